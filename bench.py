@@ -10,15 +10,21 @@ ranks (weak scaling: every rank owns its own 100k blocks = its round-robin share
 object set; no payload crosses ranks).  Counters (blocks, bytes, tag failures) are summed
 across ranks with one RCCL all-reduce after the timed region.
 
-Also reported: the dominant kernel's roofline (HBM; achieved algorithmic GB/s from HIP events
-around every xs_crypt launch inside the timed region), the CPU baseline (the oracle's
-C restatement, OpenMP, on this host's cores, bounded sample), and -- after the headline timing,
-outside it -- BASELINE configs[3] as the `objectset` key: a 1 TiB object round-robin over the N
-ranks (fixed total work: strong scaling), generated, sealed, opened and verified, with a tag
-digest that must equal the one-GPU digest (rclone_amd.objectset.CONFIG3_TAG_DIGEST) -- see
-DESIGN.md.
+A plain run sets up, checks one step's round trip, warms up, times the steps and prints the
+line: the headline figure and what falls out of the timed region itself (the dominant kernel's
+roofline from HIP events around every xs_crypt launch, clock, power).  --dump-outputs DIR writes
+what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--no-cpu] [--objectset-steps S]
+--full adds everything that takes work of its own, outside the timing: sampled blocks and the
+headline set's tag digest against the CPU oracle, the CPU baseline (the oracle's C restatement,
+OpenMP, on this host's cores, bounded sample), the engine pool check, and BASELINE configs[3]
+as the `objectset` key: a 1 TiB object round-robin over the N ranks (fixed total work: strong
+scaling), generated, sealed, opened and verified, with a tag digest that must equal the one-GPU
+digest (rclone_amd.objectset.CONFIG3_TAG_DIGEST) -- see DESIGN.md.  The secondary modes
+(--object-blocks, --mixed-gib, --names) run their CPU legs under --full too.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--objectset-steps S] [--no-pool-check]]
 """
 import argparse
 import ctypes
@@ -62,7 +68,13 @@ def parse():
     ap.add_argument("--independent", action="store_true",
                     help="configs[1] as independent one-block objects, each with its own random nonce "
                          "(default: the rank's share of one object, nonce0 + block index)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timing, also run what the headline figure does not need: the CPU oracle "
+                         "checks and baseline, the configs[3] objectset leg and the engine pool check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (wire blocks, opened "
+                         "plaintext, tag verdicts; a fixed seeded sample of blocks) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU oracle checks and baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--object-blocks", type=int, default=0,
                     help="configs[3] mode: one logical object of this many blocks (2^24 = 1 TiB) split "
@@ -406,6 +418,52 @@ def energy_per_gib(rows, total_bytes):
     if not js or any(j is None for j in js) or not total_bytes:
         return None
     return round(sum(js) / (total_bytes / 2**30), 4)
+
+
+DUMP_SEED = 0xD0E5
+DUMP_BLOCKS = 48         # whole blocks kept (wire and opened): 2 x 48 x 64 KiB x 4 B = 25 MB as float32
+DUMP_TAG_ROWS = 1 << 18  # blocks whose 16-byte tag and verdict are kept: at most 17 + 1 MB
+
+
+def dump_sample(nb):
+    """The local block indices --dump-outputs keeps of an nb-block set, sorted: (whole blocks,
+    tag/verdict rows).  A function of nb alone."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    if nb <= DUMP_BLOCKS:
+        blocks = np.arange(nb, dtype=np.int64)
+    else:
+        picked = rng.choice(nb, DUMP_BLOCKS - 2, replace=False)
+        blocks = np.unique(np.concatenate([[0, nb - 1], picked])).astype(np.int64)
+    if nb <= DUMP_TAG_ROWS:
+        rows = np.arange(nb, dtype=np.int64)
+    else:
+        rows = np.sort(rng.choice(nb, DUMP_TAG_ROWS, replace=False)).astype(np.int64)
+    return blocks, rows
+
+
+def dump_outputs(path, rank, nb, body, out, ok):
+    """--dump-outputs: what the last timed step handed back -- the sealed wire blocks (`body`), the
+    opened plaintext (`out`) and the per-block tag verdicts (`ok`) -- as float32 .npy files, one
+    byte per element, under 64 MB in all.  The full set is 13 GB, so whole blocks are a fixed seeded
+    sample (first, last, DUMP_BLOCKS in all); the Poly1305 tag, which depends on every byte of its
+    block, and the verdict are kept for every block up to DUMP_TAG_ROWS (a seeded sample beyond).
+    The inputs are seeded too, so the same arguments give the same files on any correct build.
+    Rank 0 writes <name>.npy, rank r > 0 <name>.rank<r>.npy."""
+    import numpy as np
+    import torch
+    blocks, rows = dump_sample(nb)
+    bi = torch.from_numpy(blocks).to(body.device)
+    ri = torch.from_numpy(rows).to(body.device)
+    wire = body.view(nb, BLOCK_SIZE)
+    arrays = {"wire_blocks": wire.index_select(0, bi),                # 16-byte tag + 65536 ciphertext bytes each
+              "opened_blocks": out.view(nb, BLOCK_DATA).index_select(0, bi),
+              "wire_tags": wire[:, :16].index_select(0, ri),
+              "tag_ok": ok.index_select(0, ri)}
+    os.makedirs(path, exist_ok=True)
+    suffix = ".npy" if rank == 0 else f".rank{rank}.npy"
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + suffix), t.cpu().numpy().astype(np.float32))
 
 
 def headline_expected_digest(world, nb, independent):
@@ -763,7 +821,7 @@ def run_mixed(args, world, rank, dev, dist):
 
     seal(wire_a)
     torch.cuda.synchronize(dev)
-    if rank == 0 and not args.no_cpu:  # the oracle checks sampled blocks (never timed)
+    if rank == 0 and args.cpu:  # the oracle checks sampled blocks (never timed)
         from oracle import pyoracle as orc
         partial = int(np.flatnonzero(d["len"] < BLOCK_DATA)[0])
         carry = int(np.flatnonzero(obj == 0)[-1])  # object 0's nonce carries out of byte 7
@@ -971,7 +1029,7 @@ def run_names(args, world, rank):
                        "kernel_names_per_s": round(n / (ke * 1e-3))},
             "cpu_baseline": None,
         }
-        if not args.no_cpu and world == 1:  # the CPU baseline is an N=1 figure (rank 0 only)
+        if args.cpu and world == 1:  # the CPU baseline is an N=1 figure (rank 0 only)
             res["cpu_baseline"] = names_cpu_baseline(segs, c.name_key, c.name_tweak, 5.0)
         print(json.dumps(res), flush=True)
     if grouped(world):
@@ -983,6 +1041,11 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench: --steps must be >= 1")
+    if args.dump_outputs and (args.object_blocks or args.names or args.mixed_gib or args.dry_run):
+        raise SystemExit("bench: --dump-outputs writes the default mode's outputs only")
+    args.cpu = args.full and not args.no_cpu  # the CPU oracle's checks and baselines
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1090,7 +1153,7 @@ def main():
     torch.cuda.synchronize(dev)
     if not (torch.equal(out, plain) and int(ok.sum()) == nb):
         raise SystemExit("bench: round trip failed on rank %d" % rank)
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.cpu:
         from oracle import pyoracle as orc
         for j, i in enumerate([0, 1, nb // 2, nb - 1]):
             p = plain[i * BLOCK_DATA:(i + 1) * BLOCK_DATA].cpu().numpy().tobytes()
@@ -1138,7 +1201,8 @@ def main():
     from rclone_amd.objectset import tag_digest
     counters = torch.tensor([args.steps * 2 * nb, args.steps * 2 * plain_len, int(nb - int(ok.sum())), 0, 0],
                             dtype=torch.int64, device=dev)
-    counters[3:5] = tag_digest(body, nb)  # order-independent: the same for any world size
+    if args.full:
+        counters[3:5] = tag_digest(body, nb)  # order-independent: the same for any world size
     tmax = torch.tensor([el], dtype=torch.float64, device=dev)
     shard.reduce_counters(counters, dist if grouped(world) else None)
     if grouped(world):
@@ -1152,11 +1216,17 @@ def main():
     rows = per_rank(dist, world, rank, dev, [el_rank, seal_avg, open_avg, watts, joules, sclk])
     # the headline set's tag digest against the CPU oracle's (tests/golden/fullsize.json), for the
     # layouts it pins: --blocks 100000 at 1/2/4/8 ranks, one object (not --independent)
-    digest = "%016x%016x" % (int(counters[4].item()) & (2**64 - 1), int(counters[3].item()) & (2**64 - 1))
-    expect = headline_expected_digest(world, nb, args.independent)
+    # (--full only: a plain run reports neither digest and takes no oracle pin)
+    digest = "%016x%016x" % (int(counters[4].item()) & (2**64 - 1), int(counters[3].item()) & (2**64 - 1)) \
+        if args.full else None
+    expect = headline_expected_digest(world, nb, args.independent) if args.full else None
     digest_ok = expect is None or digest == expect
+    # what the last timed step computed, for an output-for-output comparison of two builds
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, nb, body, out, ok)
     # configs[3] leg: every rank, after the headline's timing and reduction (never inside them)
-    objset, objset_ok = objectset_leg(args, world, rank, dev, dist) if args.objectset_steps > 0 else (None, None)
+    objset, objset_ok = (objectset_leg(args, world, rank, dev, dist) if args.full and args.objectset_steps > 0
+                         else (None, None))
     if os.environ.get("BENCH_TRACE"):
         print("seal_ms", [round(x, 3) for x in seal_ms], "\nopen_ms", [round(x, 3) for x in open_ms],
               file=sys.stderr)
@@ -1230,7 +1300,8 @@ def main():
             "warmup_s": round(warm_s, 3), "warmup_steps": nwarm,
             "counters": {"blocks": int(counters[0].item()), "bytes": total_bytes,
                          "tag_failures": int(counters[2].item()),
-                         "tag_digest": digest, "tag_digest_expected": expect, "tag_digest_ok": digest_ok,
+                         "tag_digest": digest, "tag_digest_expected": expect,
+                         "tag_digest_ok": digest_ok if args.full else None,
                          "digest_source": "summed over ranks; expected = CPU oracle, tests/golden/fullsize.json "
                                           "bench_headline (tests/golden/make_fullsize.py)"},
             "cpu_baseline": None,
@@ -1241,9 +1312,9 @@ def main():
     if grouped(world):
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_cpu and world == 1:  # the CPU baseline is an N=1 figure (rank 0 only)
+        if args.cpu and world == 1:  # the CPU baseline is an N=1 figure (rank 0 only)
             res["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
-        if not args.no_pool_check:
+        if args.full and not args.no_pool_check:
             res["pool_check"] = pool_check()
         print(json.dumps(res), flush=True)
     fail_if_wrong(digest_ok, digest, expect, int(counters[2].item()), objset_ok)

@@ -18,7 +18,8 @@ def _bench(*args):
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", *args],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1",
+                        *args],
                        capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -54,7 +55,7 @@ def test_bench_wrong_result_fails_the_run(force, why):
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
     env = dict(os.environ, BENCH_FORCE_DIGEST_MISMATCH=force, BENCH_OBJECTSET_BLOCKS="200000")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                         "--warmup-seconds", "0", "--blocks", "100000", "--no-cpu", "--no-pool-check",
                         "--objectset-steps", "1", "--objectset-warmup", "0"],
                        capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
@@ -74,7 +75,7 @@ def test_bench_default_line_pins_and_measurements():
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "4",
                         "--warmup-seconds", "0.5", "--no-cpu", "--no-pool-check", "--objectset-steps", "0"],
                        capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]

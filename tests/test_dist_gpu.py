@@ -38,7 +38,8 @@ def _bench(*args, gloo=True, env_extra=None):
     if gloo:
         env["BENCH_DIST_BACKEND"] = "gloo"
     env.update(env_extra or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--warmup-seconds", "0", "--no-cpu", *args],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--warmup-seconds", "0", "--no-cpu",
+                        *args],
                        capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]

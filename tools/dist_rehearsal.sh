@@ -2,13 +2,14 @@
 # the GPU) in every mode; each line must carry n_gpus = ranks_seen = N.  The same checks run in
 # the -m gpu suite (tests/test_dist_gpu.py); this script keeps the full-size lines.
 set -o pipefail
-mkdir -p gpurun_out
+OUT=${DIST_OUT:-bench_out}  # where the lines are kept
+mkdir -p $OUT
 export BENCH_DIST_BACKEND=gloo
-run() {  # name, args...
+run() {  # name, args...  (--full: the lines carry the oracle digests and the configs[3] leg)
   local name=$1; shift
-  timeout -k 10 300 python bench.py --no-cpu "$@" > gpurun_out/$name.json 2> gpurun_out/$name.err || { echo FAIL $name; tail -30 gpurun_out/$name.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo FAIL $name; tail -30 $OUT/$name.err; exit 1; }
   python3 -c "
-import json,sys; d=json.loads(open('gpurun_out/$name.json').read().strip().splitlines()[-1]); c=d['config']
+import json,sys; d=json.loads(open('$OUT/$name.json').read().strip().splitlines()[-1]); c=d['config']
 assert d['n_gpus']==c['ranks_seen'], d
 k=d.get('counters') or {}; o=d.get('objectset') or {}
 assert k.get('tag_digest_ok', True) and o.get('ok', True), (k, o)

@@ -20,11 +20,11 @@ grep -E "^configs\[(3|4)\]" $OUT/gpu_tests.log
 tail -2 $OUT/gpu_tests.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo SMOKE_FAILED; cat $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail $OUT/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo BENCH_FAILED; tail $OUT/bench.err; exit 1; }
 cut -c1-400 $OUT/bench.json
 fi
 if [ -n "$BENCH2" ]; then
-BENCH_DIST_BACKEND=gloo timeout -k 10 400 python3 bench.py --gpus 2 --no-cpu > $OUT/bench2.json 2> $OUT/bench2.err || { echo BENCH2_FAILED; tail $OUT/bench2.err; exit 1; }
+BENCH_DIST_BACKEND=gloo timeout -k 10 400 python3 bench.py --full --gpus 2 --no-cpu > $OUT/bench2.json 2> $OUT/bench2.err || { echo BENCH2_FAILED; tail $OUT/bench2.err; exit 1; }
 cut -c1-300 $OUT/bench2.json
 fi
 if [ -n "$PROF" ]; then
@@ -42,8 +42,7 @@ done
 cd $R && python3 tools/pmc_summary.py $OUT/pmc > $OUT/pmc_summary.json && echo PMC_DONE
 fi
 if [ -n "$DIST" ]; then
-cd $R && DIST8=1 bash tools/dist_rehearsal.sh > $OUT/dist_rehearsal.log 2>&1 || { echo DIST_FAILED; tail -30 $OUT/dist_rehearsal.log; exit 1; }
+cd $R && DIST8=1 DIST_OUT=$OUT bash tools/dist_rehearsal.sh > $OUT/dist_rehearsal.log 2>&1 || { echo DIST_FAILED; tail -30 $OUT/dist_rehearsal.log; exit 1; }
 cat $OUT/dist_rehearsal.log
-for f in dist2 dist4 dist8 dist8_objset; do cp gpurun_out/$f.json $OUT/ 2>/dev/null; done
 fi
 echo CLOSING_DONE
