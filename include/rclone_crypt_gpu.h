@@ -146,6 +146,26 @@ int xs_clock_probe_dev(const uint32_t *d_stop, uint64_t *d_out, double max_secon
 int xs_md5_batch_dev(const xs_md5_desc *d_desc, uint64_t n, const void *d_src, uint64_t src_len,
                      uint8_t *d_digest, uint8_t *d_ok, void *stream);
 
+/* Hash types.  Fs.put and cryptcheck hash the ciphertext with the wrapped remote's
+ * Hashes().GetOne() (crypt.go:516, cmd/cryptcheck/cryptcheck.go:74-79): MD5 where the remote has
+ * it, SHA-1 for Backblaze B2, Box and the other SHA-1-only remotes (fs/hash/hash.go:123-127).  The
+ * values are rclone's own hash.Type values (1 << registration index, fs/hash/hash.go:43), so a
+ * binding passes its hashType through.  Every *_hash / *_type entry point below is the MD5 entry
+ * point of the same name with the type added; any other type is XS_ERR_INVALID / RC_ERR_INVALID
+ * with a message in xs_last_error, and nothing is launched. */
+#define XS_HASH_MD5 1
+#define XS_HASH_SHA1 2
+typedef xs_md5_desc xs_hash_desc;
+/* Digest bytes of a hash type: 16, 20, or 0 for an unknown type. */
+size_t xs_hash_size(int type);
+/* xs_md5_batch_dev for either type: d_digest[xs_hash_size(type)*i] = H(prefix_i || src[off_i :
+ * off_i+len_i]), SHA-1 digests in FIPS 180-4 byte order.  d_digest must be 4-byte aligned. */
+int xs_hash_batch_dev(int type, const xs_hash_desc *d_desc, uint64_t n, const void *d_src, uint64_t src_len,
+                      uint8_t *d_digest, uint8_t *d_ok, void *stream);
+/* One-shot digest of p[0:n] on the calling thread: what the host tier computes for the objects
+ * routed off the GPU lanes.  Needs no GPU. */
+int xs_host_hash(int type, const void *p, uint64_t n, uint8_t *out);
+
 /* Host-memory engine: pinned staging, per-slot streams, H2D/kernel/D2H overlapped. */
 typedef struct xs_engine xs_engine;
 xs_engine *xs_engine_create(int device, uint32_t batch_blocks, int nslots);
@@ -186,6 +206,14 @@ int xs_engine_put_batch(xs_engine *e, const uint8_t key[32], uint64_t nobj, cons
                         const uint64_t *offs, const uint64_t *lens, const void *plain, void *body,
                         uint8_t *md5);
 uint64_t xs_put_body_bytes(uint64_t nobj, const uint64_t *lens);
+/* xs_engine_seal_md5 / xs_engine_put_batch with the wrapped remote's hash type: digest is packed at
+ * stride xs_hash_size(type).  Routing of long objects to host cores works as for MD5, with the
+ * SHA-1 lane and host rates (xs_engine_set_host_md5 and xs_engine_md5_stats cover either type). */
+int xs_engine_seal_hash(xs_engine *e, int type, const uint8_t key[32], uint64_t nobj, const uint8_t *nonces,
+                        const uint64_t *offs, const uint64_t *lens, const void *plain, uint8_t *digest);
+int xs_engine_put_batch_hash(xs_engine *e, int type, const uint8_t key[32], uint64_t nobj, const uint8_t *nonces,
+                             const uint64_t *offs, const uint64_t *lens, const void *plain, void *body,
+                             uint8_t *digest);
 /* Cross-caller coalescing (default on; env XS_ENGINE_COALESCE=0 or this call turns it off):
  * concurrent xs_engine_seal/xs_engine_open callers whose request fits one engine batch are
  * packed into one combined GPU batch (group commit: the first caller in leads, the others
@@ -219,6 +247,11 @@ int xs_pool_seal_md5(xs_pool *p, const uint8_t key[32], uint64_t nobj, const uin
                      const uint64_t *offs, const uint64_t *lens, const void *plain, uint8_t *md5);
 int xs_pool_put_batch(xs_pool *p, const uint8_t key[32], uint64_t nobj, const uint8_t *nonces,
                       const uint64_t *offs, const uint64_t *lens, const void *plain, void *body, uint8_t *md5);
+int xs_pool_seal_hash(xs_pool *p, int type, const uint8_t key[32], uint64_t nobj, const uint8_t *nonces,
+                      const uint64_t *offs, const uint64_t *lens, const void *plain, uint8_t *digest);
+int xs_pool_put_batch_hash(xs_pool *p, int type, const uint8_t key[32], uint64_t nobj, const uint8_t *nonces,
+                           const uint64_t *offs, const uint64_t *lens, const void *plain, void *body,
+                           uint8_t *digest);
 
 /* Pinned (page-locked) host memory. */
 void *xs_host_alloc(size_t bytes);
@@ -334,6 +367,13 @@ void rc_encrypter_nonce(const rc_encrypter *e, uint8_t out[24]);
  * far -- what hasher.Sums() gives after the wrapped Put -- or RC_ERR_INVALID if the option is off. */
 int32_t rc_encrypter_set_md5(rc_encrypter *e, int32_t on);
 int32_t rc_encrypter_md5(rc_encrypter *e, uint8_t out[16]);
+/* The same tee with the wrapped remote's hash type (XS_HASH_MD5 / XS_HASH_SHA1; 0 turns the hash
+ * off; any other value is RC_ERR_INVALID), before the first read only.  One type per encrypter: a
+ * second call replaces the first.  rc_encrypter_hash writes the xs_hash_size(type)-byte digest of
+ * exactly the bytes returned so far; RC_ERR_INVALID if the hash is off or cap is too small.
+ * rc_encrypter_set_md5(e, on) / rc_encrypter_md5 are the MD5 case of these two. */
+int32_t rc_encrypter_set_hash(rc_encrypter *e, int32_t type);
+int32_t rc_encrypter_hash(rc_encrypter *e, uint8_t *out, uint64_t cap);
 void rc_encrypter_free(rc_encrypter *e);
 
 /* newDecrypter / DecryptData (:793, :1099) */
@@ -376,6 +416,14 @@ int32_t rc_hash_batch_with_nonce(rc_cipher *c, uint64_t n, const rc_reader *srcs
  * "failed to hash data: %w"); the closer's error when every read succeeded -- md5 is then set too,
  * as the reference returns hashStr alongside CheckClose's error; or RC_ERR_GPU. */
 int32_t rc_compute_hash_with_nonce(rc_cipher *c, rc_reader src, const uint8_t nonce[24], uint8_t md5[16]);
+/* The two calls above for the wrapped remote's hash type (crypt.go:790 hashes with
+ * f.Fs.Hashes().GetOne()): digest is packed at stride xs_hash_size(type) in the batched call and
+ * holds xs_hash_size(type) bytes in the per-object call.  Reads, closes, errors and RC_ERR_GPU are
+ * as above; an unknown type is RC_ERR_INVALID before any source is read. */
+int32_t rc_hash_batch_with_nonce_type(rc_cipher *c, int32_t type, uint64_t n, const rc_reader *srcs,
+                                      const uint8_t *nonces, uint8_t *digest, int32_t *errs);
+int32_t rc_compute_hash_with_nonce_type(rc_cipher *c, int32_t type, rc_reader src, const uint8_t nonce[24],
+                                        uint8_t *digest);
 
 /* ------------------------------------------------------------------------------------
  * File-name cipher (cipher.go:120-618): NameEncryptionMode, fileNameEncoding, encryptSegment /

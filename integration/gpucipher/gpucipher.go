@@ -26,6 +26,10 @@ rc_decrypter *gpucipher_decrypt_seek(rc_cipher *c, uintptr_t open_state, int64_t
 int32_t gpucipher_compute_hash(rc_cipher *c, uintptr_t src, int closer, const uint8_t *nonce, uint8_t *md5);
 int32_t gpucipher_hash_batch(rc_cipher *c, uint64_t n, const uintptr_t *srcs, uint64_t n_nonces, const uint8_t *nonces,
                              uint8_t *md5, int32_t *errs);
+int32_t gpucipher_compute_hash_type(rc_cipher *c, int32_t type, uintptr_t src, int closer, const uint8_t *nonce,
+                                    uint8_t *digest);
+int32_t gpucipher_hash_batch_type(rc_cipher *c, int32_t type, uint64_t n, const uintptr_t *srcs, uint64_t n_nonces,
+                                  const uint8_t *nonces, uint8_t *digest, int32_t *errs);
 */
 import "C"
 
@@ -269,36 +273,53 @@ func New(dataKey, nameKey *[32]byte, nameTweak *[16]byte, passBadBlocks bool) (*
 	return c, nil
 }
 
-// ComputeHashWithNonce is computeHashWithNonce (crypt.go:784-806) for MD5 after src.Open: in is
+// HashMD5 and HashSHA1 are the hash types the library computes: rclone's own hash.MD5 and hash.SHA1
+// values (fs/hash/hash.go:43), so backend/crypt passes int32(hashType) through.
+const (
+	HashMD5  int32 = C.XS_HASH_MD5
+	HashSHA1 int32 = C.XS_HASH_SHA1
+)
+
+// ComputeHashWithNonce is ComputeHashWithNonceType for MD5.
+func (c *Cipher) ComputeHashWithNonce(nonce *[24]byte, in io.Reader) (hashStr string, err error) {
+	return c.ComputeHashWithNonceType(HashMD5, nonce, in)
+}
+
+// ComputeHashWithNonceType is computeHashWithNonce (crypt.go:784-806) after src.Open, for the
+// wrapped remote's hash type (MD5, or SHA-1 for Backblaze B2, Box and the like): in is
 // read to EOF, sealed with nonce on the GPU -- concurrent checkers' seals share launches -- and
-// "RCLONE\0\0" || nonce || wire blocks is MD5'd on host cores; in is closed when it is an
+// "RCLONE\0\0" || nonce || wire blocks is hashed on host cores; in is closed when it is an
 // io.Closer (the library does what `defer fs.CheckClose(in, &err)` does).  It returns what the
 // reference returns from that point: ("", "failed to hash data: %w") for a read error, the hex
 // digest and nil, or the hex digest with the close error.  crypt.go's change, after src.Open:
 //
-//	if f.cipher.gpu != nil && hashType == hash.MD5 {
-//		return f.cipher.gpu.ComputeHashWithNonce((*[24]byte)(&nonce), in)
+//	if f.cipher.gpu != nil && (hashType == hash.MD5 || hashType == hash.SHA1) {
+//		return f.cipher.gpu.ComputeHashWithNonceType(int32(hashType), (*[24]byte)(&nonce), in)
 //	}
 //	defer fs.CheckClose(in, &err) // the Go path, unchanged
-func (c *Cipher) ComputeHashWithNonce(nonce *[24]byte, in io.Reader) (hashStr string, err error) {
-	var sum [16]byte
+func (c *Cipher) ComputeHashWithNonceType(hashType int32, nonce *[24]byte, in io.Reader) (hashStr string, err error) {
+	size := int(C.xs_hash_size(C.int(hashType)))
+	if size == 0 {
+		return "", fmt.Errorf("gpucipher: unsupported hash type %d", hashType)
+	}
+	sum := make([]byte, size)
 	t := &errTable{}
 	box := &readerBox{r: in, t: t}
 	hd := cgo.NewHandle(box)
 	defer hd.Delete()
 	_, closer := in.(io.Closer)
-	rc := C.gpucipher_compute_hash(c.h, C.uintptr_t(hd), cbool(closer), (*C.uint8_t)(unsafe.Pointer(&nonce[0])),
-		(*C.uint8_t)(unsafe.Pointer(&sum[0])))
+	rc := C.gpucipher_compute_hash_type(c.h, C.int32_t(hashType), C.uintptr_t(hd), cbool(closer),
+		(*C.uint8_t)(unsafe.Pointer(&nonce[0])), (*C.uint8_t)(unsafe.Pointer(&sum[0])))
 	runtime.KeepAlive(c)
 	switch {
 	case rc == C.RC_NIL:
-		return hex.EncodeToString(sum[:]), nil
+		return hex.EncodeToString(sum), nil
 	case rc == C.RC_ERR_GPU:
 		return "", fmt.Errorf("failed to hash data: gpucipher: %s", C.GoString(C.xs_last_error()))
 	case box.readErr || !closer:
 		return "", fmt.Errorf("failed to hash data: %w", t.err(rc)) // io.Copy's error
 	default:
-		return hex.EncodeToString(sum[:]), t.err(rc) // every read succeeded: CheckClose's error
+		return hex.EncodeToString(sum), t.err(rc) // every read succeeded: CheckClose's error
 	}
 }
 
@@ -311,6 +332,8 @@ type Encrypter struct {
 	t    *errTable
 	hd   cgo.Handle
 	done sync.Once // hd deleted: the stream has finished and the library reads its source no more
+	// hashType is the tee hash's type once SetMD5 / SetHash succeeded (0: off)
+	hashType int32
 }
 
 // NewEncrypter is newEncrypter(in, nonce) (cipher.go:694).  The nonce must be given: the
@@ -344,6 +367,7 @@ func (fh *Encrypter) SetMD5() error {
 	if rc != C.RC_NIL {
 		return errors.New("gpucipher: SetMD5 after the first Read")
 	}
+	fh.hashType = HashMD5
 	return nil
 }
 
@@ -355,6 +379,34 @@ func (fh *Encrypter) MD5() (sum [16]byte, err error) {
 		return sum, errors.New("gpucipher: MD5 without SetMD5")
 	}
 	return sum, nil
+}
+
+// SetHash is SetMD5 for the wrapped remote's hash type (HashMD5, HashSHA1); put uses Hash() as
+// srcHash.
+func (fh *Encrypter) SetHash(hashType int32) error {
+	rc := C.rc_encrypter_set_hash(fh.h, C.int32_t(hashType))
+	runtime.KeepAlive(fh)
+	if rc != C.RC_NIL {
+		return errors.New("gpucipher: SetHash after the first Read, or an unsupported hash type")
+	}
+	fh.hashType = hashType
+	return nil
+}
+
+// Hash is the digest, of the type given to SetHash, of exactly the bytes Read has returned.
+func (fh *Encrypter) Hash() ([]byte, error) {
+	var buf [20]byte
+	rc := C.rc_encrypter_hash(fh.h, (*C.uint8_t)(unsafe.Pointer(&buf[0])), C.uint64_t(len(buf)))
+	runtime.KeepAlive(fh)
+	if rc != C.RC_NIL {
+		return nil, errors.New("gpucipher: Hash without SetHash")
+	}
+	// the digest's length is its type's: an MD5 leaves the last four bytes unwritten
+	n := 20
+	if fh.hashType == HashMD5 {
+		n = 16
+	}
+	return buf[:n:n], nil
 }
 
 // Read as per io.Reader (cipher.go:719): the library copies into p and never retains it.
@@ -518,6 +570,24 @@ func (fh *Decrypter) Nonce() (n [24]byte) {
 // each source is read to EOF, closed (fs.CheckClose), sealed with its nonce and its crypt file
 // MD5'd on the GPU.  errs[i] is the reference's "failed to hash data: %w" for a failing source.
 func (c *Cipher) HashBatchWithNonce(nonces [][24]byte, srcs []io.ReadCloser) (sums [][16]byte, errs []error, err error) {
+	raw, errs, err := c.HashBatchWithNonceType(HashMD5, nonces, srcs)
+	if err != nil || raw == nil {
+		return nil, errs, err
+	}
+	sums = make([][16]byte, len(raw))
+	for i := range raw {
+		copy(sums[i][:], raw[i])
+	}
+	return sums, errs, nil
+}
+
+// HashBatchWithNonceType is HashBatchWithNonce for the wrapped remote's hash type (HashMD5,
+// HashSHA1): sums[i] holds 16 or 20 bytes.
+func (c *Cipher) HashBatchWithNonceType(hashType int32, nonces [][24]byte, srcs []io.ReadCloser) (sums [][]byte, errs []error, err error) {
+	size := int(C.xs_hash_size(C.int(hashType)))
+	if size == 0 {
+		return nil, nil, fmt.Errorf("gpucipher: unsupported hash type %d", hashType)
+	}
 	n := len(srcs)
 	if len(nonces) != n {
 		// fewer nonces would hash sources with zero nonces and report false differences
@@ -543,17 +613,17 @@ func (c *Cipher) HashBatchWithNonce(nonces [][24]byte, srcs []io.ReadCloser) (su
 	for i := range nonces {
 		copy(flat[24*i:], nonces[i][:])
 	}
-	md5 := make([]byte, 16*n)
+	dig := make([]byte, size*n)
 	codes := make([]C.int32_t, n)
-	rc := C.gpucipher_hash_batch(c.h, C.uint64_t(n), &handles[0], C.uint64_t(len(nonces)),
-		(*C.uint8_t)(unsafe.Pointer(&flat[0])), (*C.uint8_t)(unsafe.Pointer(&md5[0])), &codes[0])
+	rc := C.gpucipher_hash_batch_type(c.h, C.int32_t(hashType), C.uint64_t(n), &handles[0], C.uint64_t(len(nonces)),
+		(*C.uint8_t)(unsafe.Pointer(&flat[0])), (*C.uint8_t)(unsafe.Pointer(&dig[0])), &codes[0])
 	runtime.KeepAlive(c) // the finalizer must not free c.h while the batch runs
 	if rc != C.RC_NIL {
 		return nil, nil, fmt.Errorf("gpucipher: %s", C.GoString(C.xs_last_error()))
 	}
-	sums, errs = make([][16]byte, n), make([]error, n)
+	sums, errs = make([][]byte, n), make([]error, n)
 	for i := range sums {
-		copy(sums[i][:], md5[16*i:])
+		sums[i] = dig[size*i : size*(i+1) : size*(i+1)]
 		if codes[i] != C.RC_NIL {
 			errs[i] = fmt.Errorf("failed to hash data: %w", t.err(codes[i]))
 		}

@@ -68,3 +68,21 @@ int32_t gpucipher_hash_batch(rc_cipher *c, uint64_t n, const uintptr_t *srcs, ui
   free(r);
   return rc;
 }
+
+/* The two calls above for the wrapped remote's hash type (XS_HASH_MD5 / XS_HASH_SHA1 = rclone's
+ * hash.MD5 / hash.SHA1 values): digest holds xs_hash_size(type) bytes per object. */
+int32_t gpucipher_compute_hash_type(rc_cipher *c, int32_t type, uintptr_t src, int closer, const uint8_t *nonce,
+                                    uint8_t *digest) {
+  return rc_compute_hash_with_nonce_type(c, type, gpucipher_reader(src, closer, 0), nonce, digest);
+}
+
+int32_t gpucipher_hash_batch_type(rc_cipher *c, int32_t type, uint64_t n, const uintptr_t *srcs, uint64_t n_nonces,
+                                  const uint8_t *nonces, uint8_t *digest, int32_t *errs) {
+  if (n_nonces != n) return RC_ERR_INVALID;
+  rc_reader *r = (rc_reader *)malloc((n ? n : 1) * sizeof *r);
+  if (!r) return RC_ERR_INVALID;
+  for (uint64_t i = 0; i < n; i++) r[i] = gpucipher_reader(srcs[i], 1, 0);
+  const int32_t rc = rc_hash_batch_with_nonce_type(c, type, n, r, nonces, digest, errs);
+  free(r);
+  return rc;
+}

@@ -59,6 +59,9 @@ _SIGS = [
     ("xs_fill_blocks_dev", ctypes.c_int, [vp, u64, u64, u64, u64, vp]),
     ("xs_verify_blocks_dev", ctypes.c_int, [vp, u64, u64, u64, u64, vp, vp]),
     ("xs_md5_batch_dev", ctypes.c_int, [vp, u64, vp, u64, vp, vp, vp]),
+    ("xs_hash_size", ctypes.c_size_t, [ctypes.c_int]),
+    ("xs_hash_batch_dev", ctypes.c_int, [ctypes.c_int, vp, u64, vp, u64, vp, vp, vp]),
+    ("xs_host_hash", ctypes.c_int, [ctypes.c_int, vp, u64, vp]),
     ("xs_clock_probe_dev", ctypes.c_int, [vp, vp, ctypes.c_double, vp]),
     ("xs_engine_create", vp, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int]),
     ("xs_engine_destroy", None, [vp]),
@@ -67,6 +70,8 @@ _SIGS = [
     ("xs_engine_open_range", ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_char_p, u64, vp, u64, vp, vp, u64, u64]),
     ("xs_engine_seal_md5", ctypes.c_int, [vp, ctypes.c_char_p, u64, vp, vp, vp, vp, vp]),
     ("xs_engine_put_batch", ctypes.c_int, [vp, ctypes.c_char_p, u64, vp, vp, vp, vp, vp, vp]),
+    ("xs_engine_seal_hash", ctypes.c_int, [vp, ctypes.c_int, ctypes.c_char_p, u64, vp, vp, vp, vp, vp]),
+    ("xs_engine_put_batch_hash", ctypes.c_int, [vp, ctypes.c_int, ctypes.c_char_p, u64, vp, vp, vp, vp, vp, vp]),
     ("xs_put_body_bytes", u64, [u64, vp]),
     ("xs_engine_set_coalesce", None, [vp, ctypes.c_int]),
     ("xs_engine_stats", None, [vp, vp]),
@@ -79,6 +84,8 @@ _SIGS = [
     ("xs_pool_next", vp, [vp]),
     ("xs_pool_seal_md5", ctypes.c_int, [vp, ctypes.c_char_p, u64, vp, vp, vp, vp, vp]),
     ("xs_pool_put_batch", ctypes.c_int, [vp, ctypes.c_char_p, u64, vp, vp, vp, vp, vp, vp]),
+    ("xs_pool_seal_hash", ctypes.c_int, [vp, ctypes.c_int, ctypes.c_char_p, u64, vp, vp, vp, vp, vp]),
+    ("xs_pool_put_batch_hash", ctypes.c_int, [vp, ctypes.c_int, ctypes.c_char_p, u64, vp, vp, vp, vp, vp, vp]),
     ("xs_host_alloc", vp, [ctypes.c_size_t]),
     ("xs_host_alloc_node", vp, [ctypes.c_size_t, ctypes.c_int]),
     ("xs_device_numa_node", ctypes.c_int, [ctypes.c_int]),
@@ -113,6 +120,8 @@ _SIGS = [
     ("rc_encrypter_free", None, [vp]),
     ("rc_encrypter_set_md5", i32, [vp, i32]),
     ("rc_encrypter_md5", i32, [vp, vp]),
+    ("rc_encrypter_set_hash", i32, [vp, i32]),
+    ("rc_encrypter_hash", i32, [vp, vp, u64]),
     ("rc_decrypt_data", vp, [vp, RcReader, ctypes.POINTER(i32)]),
     ("rc_decrypt_data_seek", vp, [vp, OPEN_FN, vp, i64, i64, ctypes.POINTER(i32)]),
     ("rc_decrypt_data_seek_ex", vp, [vp, OPEN_FN, vp, i64, i64, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
@@ -124,6 +133,8 @@ _SIGS = [
     ("rc_decrypter_free", None, [vp]),
     ("rc_hash_batch_with_nonce", i32, [vp, u64, vp, vp, vp, vp]),
     ("rc_compute_hash_with_nonce", i32, [vp, RcReader, vp, vp]),
+    ("rc_hash_batch_with_nonce_type", i32, [vp, i32, u64, vp, vp, vp, vp]),
+    ("rc_compute_hash_with_nonce_type", i32, [vp, i32, RcReader, vp, vp]),
     ("rc_error_string", ctypes.c_char_p, [i32]),
     # file names (cipher.go:120-618)
     ("xs_eme_batch_dev", ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, vp, u64, vp, vp, u64, vp]),

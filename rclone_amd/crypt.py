@@ -38,6 +38,20 @@ FILE_MAGIC = b"RCLONE\x00\x00"
 
 RC_NIL, RC_EOF, RC_UNEXPECTED_EOF, RC_USER_BASE = 0, 1, 2, 16
 
+# hash types of the ciphertext hash: rclone's hash.Type values (fs/hash/hash.go:43), XS_HASH_* of
+# include/rclone_crypt_gpu.h
+HASH_MD5, HASH_SHA1 = 1, 2
+HASH_TYPES = {"md5": HASH_MD5, "sha1": HASH_SHA1}
+HASH_SIZES = {HASH_MD5: 16, HASH_SHA1: 20}
+
+
+def hash_type_id(name) -> int:
+    """"md5" / "sha1" (hash.Type.String()) or the numeric type -> XS_HASH_*; ValueError otherwise."""
+    ht = HASH_TYPES.get(name, name)
+    if ht not in HASH_SIZES:
+        raise ValueError(f"unsupported hash type {name!r} (md5, sha1)")
+    return ht
+
 
 class _EOF:
     """io.EOF marker for read_go() readers."""
@@ -348,11 +362,14 @@ class Cipher(NameCipherMixin):
         return Decrypter(self, None, open_fn=open_fn, offset=offset, limit=limit)
 
     # ---------------------------------------------------------------- hashes (crypt.go:784-852)
-    def hash_batch_with_nonce(self, items):
-        """Fs.computeHashWithNonce (crypt.go:784) for MD5, batched: items = [(nonce, src)], src a
-        Go-style reader (closed after reading, fs.CheckClose).  Sealing and MD5 both run on the
-        GPU (rc_hash_batch_with_nonce); returns per item the 16-byte digest, or the exception
-        the source raised (the reference wraps it: "failed to hash data: %w")."""
+    def hash_batch_with_nonce(self, items, hash_type="md5"):
+        """Fs.computeHashWithNonce (crypt.go:784), batched: items = [(nonce, src)], src a
+        Go-style reader (closed after reading, fs.CheckClose).  hash_type is the wrapped remote's
+        Hashes().GetOne(): "md5" or "sha1".  Sealing and hashing both run on the GPU
+        (rc_hash_batch_with_nonce_type); returns per item the 16- or 20-byte digest, or the
+        exception the source raised (the reference wraps it: "failed to hash data: %w")."""
+        ht = hash_type_id(hash_type)
+        hs = HASH_SIZES[ht]
         n = len(items)
         if n == 0:
             return []
@@ -361,33 +378,41 @@ class Cipher(NameCipherMixin):
             raise ValueError("nonces must be 24 bytes")
         bridges = [_ReaderBridge(src, closer=True) for _, src in items]
         arr = (_lib.RcReader * n)(*[b.c for b in bridges])
-        md5 = ctypes.create_string_buffer(16 * n)
+        dig = ctypes.create_string_buffer(hs * n)
         errs = (ctypes.c_int32 * n)()
-        _raise(_lib.lib().rc_hash_batch_with_nonce(self._h, n, arr, nonces, md5, errs))
+        if ht == HASH_MD5:
+            _raise(_lib.lib().rc_hash_batch_with_nonce(self._h, n, arr, nonces, dig, errs))
+        else:
+            _raise(_lib.lib().rc_hash_batch_with_nonce_type(self._h, ht, n, arr, nonces, dig, errs))
         out = []
         for i in range(n):
-            out.append(md5.raw[16 * i:16 * i + 16] if errs[i] == RC_NIL else _ERRS.exc(errs[i]))
+            out.append(dig.raw[hs * i:hs * i + hs] if errs[i] == RC_NIL else _ERRS.exc(errs[i]))
         return out
 
-    def compute_hash_with_nonce(self, nonce: bytes, src) -> str:
-        """computeHashWithNonce (crypt.go:784): MD5 hex of src encrypted with nonce, one object per
-        call (rc_compute_hash_with_nonce: GPU seal, group-committed with concurrent callers; MD5
-        on host cores).  src is closed if it has close() (fs.CheckClose); its error is raised."""
+    def compute_hash_with_nonce(self, nonce: bytes, src, hash_type="md5") -> str:
+        """computeHashWithNonce (crypt.go:784): hex digest (hash_type "md5" or "sha1") of src
+        encrypted with nonce, one object per call (rc_compute_hash_with_nonce[_type]: GPU seal,
+        group-committed with concurrent callers; the hash on host cores).  src is closed if it has
+        close() (fs.CheckClose); its error is raised."""
+        ht = hash_type_id(hash_type)
         nb = bytes(nonce)
         if len(nb) != 24:
             raise ValueError("nonce must be 24 bytes")
         bridge = _ReaderBridge(src, closer=True)
-        md5 = ctypes.create_string_buffer(16)
-        _raise(_lib.lib().rc_compute_hash_with_nonce(self._h, bridge.c, nb, md5))
-        return md5.raw.hex()
+        dig = ctypes.create_string_buffer(HASH_SIZES[ht])
+        if ht == HASH_MD5:
+            _raise(_lib.lib().rc_compute_hash_with_nonce(self._h, bridge.c, nb, dig))
+        else:
+            _raise(_lib.lib().rc_compute_hash_with_nonce_type(self._h, ht, bridge.c, nb, dig))
+        return dig.raw.hex()
 
-    def compute_hash(self, obj, src) -> str:
+    def compute_hash(self, obj, src, hash_type="md5") -> str:
         """ComputeHash (crypt.go:816): the nonce comes from the encrypted object's header (read
         with newDecrypter, then closed), then computeHashWithNonce over src."""
         d = self.decrypt_data(obj)
         nonce = d.nonce
         d.close()
-        return self.compute_hash_with_nonce(nonce, src)
+        return self.compute_hash_with_nonce(nonce, src, hash_type)
 
 
 class EnginePool:
@@ -458,12 +483,27 @@ class Encrypter:
         """crypt.put's ciphertext tee hash taken by the encrypter (rc_encrypter_set_md5); before
         the first read only."""
         _raise(_lib.lib().rc_encrypter_set_md5(self._h, int(bool(on))))
+        self._hash_type = HASH_MD5 if on else 0
 
     def md5(self) -> bytes:
         """MD5 of exactly the bytes read so far (hasher.Sums() of the reference's TeeReader)."""
         d = ctypes.create_string_buffer(16)
         _raise(_lib.lib().rc_encrypter_md5(self._h, d))
         return d.raw
+
+    def set_hash(self, name):
+        """The tee hash with the wrapped remote's hash type: "md5", "sha1", or None to turn it off
+        (rc_encrypter_set_hash); before the first read only."""
+        ht = hash_type_id(name) if name is not None else 0
+        _raise(_lib.lib().rc_encrypter_set_hash(self._h, ht))
+        self._hash_type = ht
+
+    def hash(self) -> bytes:
+        """Digest of exactly the bytes read so far, of the type given to set_hash (or MD5 after
+        set_md5)."""
+        d = ctypes.create_string_buffer(20)
+        _raise(_lib.lib().rc_encrypter_hash(self._h, d, 20))
+        return d.raw[:HASH_SIZES.get(getattr(self, "_hash_type", 0) or HASH_MD5)]
 
     def read_go(self, n):
         """Go-style Read: returns (data, err) with err None, EOF or an exception."""

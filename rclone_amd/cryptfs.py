@@ -10,10 +10,13 @@ a13-a16), on top of the GPU cipher (rclone_amd.crypt -> librclone_crypt.so):
 * ``CryptFs.compute_hash`` Fs.ComputeHash (crypt.go:816-852).
 * ``CryptFs.cryptcheck``   cmd/cryptcheck cryptCheck (cryptcheck.go:67-117): underlying hash
                            vs ComputeHash for every pair, batched across objects so the
-                           re-encryption and the MD5 both run on the GPU.
+                           re-encryption and the hash both run on the GPU.
 
 ``MemoryRemote`` is the minimal backend/memory the tests and tools wrap (memory.go:580-646:
-MD5 hash computed on demand, Open honouring Range/Seek).  File names use crypt's "off" name
+MD5 hash computed on demand, Open honouring Range/Seek); ``MemoryRemote(hash_type="sha1")`` stands
+for a remote whose only hash is SHA-1 (Backblaze B2, Box).  The overlay hashes the ciphertext with
+the wrapped remote's ``Hashes().GetOne()`` (crypt.go:516, cryptcheck.go:74-79): MD5 where the remote
+has it, else SHA-1.  File names use crypt's "off" name
 mode (cipher.go:529: remote + ".bin"); name encryption itself is out of scope.
 """
 import hashlib
@@ -63,9 +66,13 @@ class _BytesReader:
 
 
 class MemoryRemote:
-    """Minimal backend/memory: objects are byte strings, MD5 is the supported hash."""
+    """Minimal backend/memory: objects are byte strings; `hashes` is the set of supported hash
+    types (Fs.Hashes()): MD5 as backend/memory, or SHA-1 alone as Backblaze B2 and Box."""
 
-    def __init__(self):
+    def __init__(self, hash_type: str = "md5"):
+        if hash_type not in crypt.HASH_TYPES:
+            raise ValueError(f"unsupported hash type {hash_type!r} (md5, sha1)")
+        self.hashes = (hash_type,)
         self.objects = {}
         self._hash = {}
         self.opens = []  # (remote, offset, limit) of every Open, for tests
@@ -100,7 +107,7 @@ class MemoryRemote:
 
     def hash(self, remote: str) -> str:
         if remote not in self._hash:
-            self._hash[remote] = hashlib.md5(self.objects[remote]).hexdigest()
+            self._hash[remote] = hashlib.new(self.hashes[0], self.objects[remote]).hexdigest()
         return self._hash[remote]
 
     def size(self, remote: str) -> int:
@@ -141,23 +148,37 @@ class CryptFs:
     def enc_name(remote: str) -> str:
         return remote + SUFFIX
 
+    def hash_type(self) -> str:
+        """f.Fs.Hashes().GetOne() (fs/hash/hash.go:123-127: the lowest registered type the remote
+        supports): "md5" if the wrapped remote has it, else "sha1".  A remote without a `hashes`
+        attribute is taken to be MD5's, as before."""
+        hashes = getattr(self.wrapped, "hashes", ("md5",))
+        for ht in ("md5", "sha1"):
+            if ht in hashes:
+                return ht
+        raise CryptError(f"wrapped remote supports none of md5, sha1: {hashes!r}")
+
     # -------------------------------------------------------------- Fs.put (crypt.go:497)
     def put(self, remote: str, reader, size: int = -1):
         enc = self.cipher.encrypt_data(reader)
-        hasher = None if self.ignore_checksum or self.encrypter_md5 else hashlib.md5()
+        ht = None if self.ignore_checksum else self.hash_type()
+        hasher = None if self.ignore_checksum or self.encrypter_md5 else hashlib.new(ht)
         src = enc if hasher is None else _TeeReader(enc, hasher)
         if not self.ignore_checksum and self.encrypter_md5:
-            enc.set_md5(True)
+            if ht == "md5":
+                enc.set_md5(True)
+            else:
+                enc.set_hash(ht)
         esize = crypt.encrypted_size(size) if size >= 0 else size  # ObjectInfo.Size (:1168)
         name = self.enc_name(remote)
         nonce = enc.nonce  # newObjectInfo(src, encrypter.nonce) is built before the transfer (:536)
         self.wrapped.put(name, src, esize)
         if not self.ignore_checksum:
-            src_hash = hasher.hexdigest() if hasher is not None else enc.md5().hex()
+            src_hash = hasher.hexdigest() if hasher is not None else enc.hash().hex()
             dst_hash = self.wrapped.hash(name)
             if src_hash and dst_hash and src_hash != dst_hash:
                 self.wrapped.remove(name)
-                raise CryptError(f"corrupted on transfer: md5 encrypted hashes differ src {src_hash!r} "
+                raise CryptError(f"corrupted on transfer: {ht} encrypted hashes differ src {src_hash!r} "
                                  f"vs dst {dst_hash!r}")
         return nonce
 
@@ -200,7 +221,7 @@ class CryptFs:
         return nonce
 
     def compute_hash(self, remote: str, src) -> str:
-        return self.cipher.compute_hash_with_nonce(self._nonce(remote), src)
+        return self.cipher.compute_hash_with_nonce(self._nonce(remote), src, self.hash_type())
 
     # -------------------------------------------------------------- cryptcheck (cryptcheck.go:67)
     def cryptcheck(self, sources: dict, batch: int = 4096, checkers: int = 0):
@@ -211,6 +232,7 @@ class CryptFs:
         Returns {"differ": [...], "no_hash": [...], "errors": {remote: exc}, "ok": n}."""
         res = {"differ": [], "no_hash": [], "errors": {}, "ok": 0}
         names = sorted(sources)
+        ht = self.hash_type()
         if checkers > 0:
             import threading
             lock, it = threading.Lock(), iter(names)
@@ -268,7 +290,7 @@ class CryptFs:
                     keep.append(r)
                 except Exception as e:  # "error computing hash"
                     res["errors"][r] = e
-            for r, h in zip(keep, self.cipher.hash_batch_with_nonce(items)):
+            for r, h in zip(keep, self.cipher.hash_batch_with_nonce(items, ht)):
                 if isinstance(h, BaseException):
                     res["errors"][r] = h
                 elif h.hex() != under[r]:

@@ -502,15 +502,16 @@ struct rc_encrypter {
   int64_t buf_index = 0, buf_size = 0;
   int32_t err = RC_NIL;
   bool finished = false;
-  // crypt.put's tee hash (crypt.go:516-533) taken by the encrypter itself (rc_encrypter_set_md5):
+  // crypt.put's tee hash (crypt.go:516-533) taken by the encrypter itself (rc_encrypter_set_hash;
+  // MD5 or SHA-1, the wrapped remote's Hashes().GetOne()):
   // a worker hashes batch k while the consumer reads it and the next refill seals batch k+1 into
   // the other wire buffer.  md5 covers every byte produced once `job` is done; md5_cur is the
   // state before the batch being served (for a consumer that stops inside a batch).
-  bool md5_on = false;
+  bool md5_on = false;       // the tee hash is on (either type: md5.type)
   bool md5_counted = false;  // in g_md5_streams
   bool wsel = false;  // md5_on: the batch being served is in wire2 (else wire)
   PinnedBuf wire2;
-  xs::HostMd5 md5, md5_cur;
+  xs::HashState md5, md5_cur;
   xs::Md5Job job;
 };
 
@@ -665,7 +666,7 @@ extern "C" int64_t rc_encrypter_read(rc_encrypter* fh, uint8_t* p, int64_t n, in
       pc.mark(kEncWait);
       fh->md5_cur = fh->md5;
       fh->wsel = into2;
-      fh->job.st = &fh->md5;
+      fh->md5.bind(&fh->job);
       fh->job.p = out;
       fh->job.n = (size_t)fh->buf_size;
       if (fh->buf_size < inline_md5_below(ramp)) fh->md5.update(out, (size_t)fh->buf_size);
@@ -682,26 +683,42 @@ extern "C" int64_t rc_encrypter_read(rc_encrypter* fh, uint8_t* p, int64_t n, in
 
 extern "C" void rc_encrypter_nonce(const rc_encrypter* fh, uint8_t out[24]) { memcpy(out, fh->nonce, 24); }
 
-extern "C" int32_t rc_encrypter_set_md5(rc_encrypter* fh, int32_t on) {
+// false (with the message xs_last_error returns) for anything but XS_HASH_MD5 / XS_HASH_SHA1
+static bool hash_type_ok(int32_t type, const char* who) {
+  if (type == XS_HASH_MD5 || type == XS_HASH_SHA1) return true;
+  xs::set_error("%s: unknown hash type %d (XS_HASH_MD5 = 1, XS_HASH_SHA1 = 2)", who, (int)type);
+  return false;
+}
+
+extern "C" int32_t rc_encrypter_set_hash(rc_encrypter* fh, int32_t type) {
   if (!fh) return RC_ERR_INVALID;
+  if (type != 0 && !hash_type_ok(type, "rc_encrypter_set_hash")) return RC_ERR_INVALID;
   std::lock_guard<std::mutex> g(fh->mu);
   if (!fh->in_hdr || fh->buf_index != 0 || fh->finished) return RC_ERR_INVALID;  // before the first Read only
-  fh->md5_on = on != 0;
+  fh->md5_on = type != 0;
   md5_stream_count(fh->md5_counted, fh->md5_on);
-  fh->md5 = xs::HostMd5();
+  fh->md5 = xs::HashState(fh->md5_on ? type : XS_HASH_MD5);
   fh->md5_cur = fh->md5;
   if (fh->md5_on) fh->md5.update(fh->hdr, kFileHdr);  // the header is the first "batch" served
   return RC_NIL;
 }
 
+extern "C" int32_t rc_encrypter_set_md5(rc_encrypter* fh, int32_t on) {
+  return rc_encrypter_set_hash(fh, on != 0 ? XS_HASH_MD5 : 0);
+}
+
 extern "C" int32_t rc_encrypter_md5(rc_encrypter* fh, uint8_t out[16]) {
+  return rc_encrypter_hash(fh, out, 16);  // RC_ERR_INVALID when the tee is SHA-1's (20 bytes)
+}
+
+extern "C" int32_t rc_encrypter_hash(rc_encrypter* fh, uint8_t* out, uint64_t cap) {
   if (!fh || !out) return RC_ERR_INVALID;
   std::lock_guard<std::mutex> g(fh->mu);
-  if (!fh->md5_on) return RC_ERR_INVALID;
+  if (!fh->md5_on || cap < fh->md5.size()) return RC_ERR_INVALID;
   xs::md5_wait(&fh->job);
   // MD5 of exactly the bytes returned so far, like the TeeReader: all produced bytes when the
   // current batch is used up (always so after EOF), else the state before it plus its served part
-  xs::HostMd5 h = fh->md5;
+  xs::HashState h = fh->md5;
   if (fh->buf_index < fh->buf_size && !fh->finished) {
     h = fh->md5_cur;
     h.update(enc_cur(fh), (size_t)fh->buf_index);
@@ -1073,8 +1090,22 @@ extern "C" int32_t rc_decrypter_wrapped_error(const rc_decrypter* fh) { return f
 extern "C" void rc_decrypter_free(rc_decrypter* fh) { delete fh; }
 
 // ---------------------------------------------------------------- computeHashWithNonce, batched
+// xs_api.cpp's typed batched seal + hash.  Weak: the CPU stand-ins of the engine ABI (tests/native:
+// the sanitizer builds and the CPU baselines) implement xs_pool_seal_md5 alone, so the MD5 case
+// keeps calling that and another type reports RC_ERR_GPU where the engine has no such entry point.
+extern "C" int xs_pool_seal_hash(xs_pool* p, int type, const uint8_t key[32], uint64_t nobj, const uint8_t* nonces,
+                                 const uint64_t* offs, const uint64_t* lens, const void* plain, uint8_t* digest)
+    __attribute__((weak));
+
 extern "C" int32_t rc_hash_batch_with_nonce(rc_cipher* c, uint64_t n, const rc_reader* srcs, const uint8_t* nonces,
                                             uint8_t* md5, int32_t* errs) {
+  return rc_hash_batch_with_nonce_type(c, XS_HASH_MD5, n, srcs, nonces, md5, errs);
+}
+
+extern "C" int32_t rc_hash_batch_with_nonce_type(rc_cipher* c, int32_t type, uint64_t n, const rc_reader* srcs,
+                                                 const uint8_t* nonces, uint8_t* md5, int32_t* errs) {
+  if (!hash_type_ok(type, "rc_hash_batch_with_nonce_type")) return RC_ERR_INVALID;
+  const size_t hs = type == XS_HASH_SHA1 ? 20 : 16;  // digest stride
   if (n == 0) return RC_NIL;
   if (!c || !srcs || !nonces || !md5 || !errs) return RC_ERR_INVALID;
   PinnedBuf buf;
@@ -1110,10 +1141,15 @@ extern "C" int32_t rc_hash_batch_with_nonce(rc_cipher* c, uint64_t n, const rc_r
   if (idx.empty()) return RC_NIL;  // every source failed: nothing for the GPU
   xs_pool* pool = cipher_pool(c);
   if (!pool) return RC_ERR_GPU;
-  std::vector<uint8_t> dig(16 * idx.size());
-  if (xs_pool_seal_md5(pool, c->data_key, idx.size(), ns.data(), offs.data(), lens.data(), buf.p, dig.data()) != XS_OK)
+  std::vector<uint8_t> dig(hs * idx.size());
+  if (type == XS_HASH_MD5) {
+    if (xs_pool_seal_md5(pool, c->data_key, idx.size(), ns.data(), offs.data(), lens.data(), buf.p, dig.data()) != XS_OK)
+      return RC_ERR_GPU;
+  } else if (!xs_pool_seal_hash || xs_pool_seal_hash(pool, type, c->data_key, idx.size(), ns.data(), offs.data(),
+                                                      lens.data(), buf.p, dig.data()) != XS_OK) {
     return RC_ERR_GPU;
-  for (size_t k = 0; k < idx.size(); k++) memcpy(md5 + 16 * idx[k], dig.data() + 16 * k, 16);
+  }
+  for (size_t k = 0; k < idx.size(); k++) memcpy(md5 + hs * idx[k], dig.data() + hs * k, hs);
   return RC_NIL;
 }
 
@@ -1136,19 +1172,25 @@ static uint32_t hash_batch_blocks() {
 }
 
 extern "C" int32_t rc_compute_hash_with_nonce(rc_cipher* c, rc_reader src, const uint8_t nonce[24], uint8_t md5[16]) {
+  return rc_compute_hash_with_nonce_type(c, XS_HASH_MD5, src, nonce, md5);
+}
+
+extern "C" int32_t rc_compute_hash_with_nonce_type(rc_cipher* c, int32_t type, rc_reader src, const uint8_t nonce[24],
+                                                   uint8_t* md5) {
+  if (!hash_type_ok(type, "rc_compute_hash_with_nonce_type")) return RC_ERR_INVALID;
   if (!c || !src.read || !nonce || !md5) return RC_ERR_INVALID;
   const uint32_t batch = hash_batch_blocks();
   xs_engine* eng = xs_pool_next(cipher_pool(c));
   const int node = eng ? xs_engine_numa_node(eng) : -1;
   auto& w = xs::md5_workers(node);
-  xs::HostMd5 m;
+  xs::HashState m(type);
   m.update(kMagic, 8);
   m.update(nonce, 24);
   uint8_t n[24];
   memcpy(n, nonce, 24);
   PinnedBuf plain, wire[2];
   xs::Md5Job job;
-  job.st = &m;
+  m.bind(&job);
   int32_t err = RC_NIL;
   PhaseClock pc;
   pc.count(kHashCalls);

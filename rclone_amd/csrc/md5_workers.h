@@ -13,6 +13,8 @@
 //   3. past that budget, a lane of the 16-stream AVX-512 engine (md5_x16.h): each lane runs at
 //      about half a scalar chain (0.48 GB/s on Zen 5) but a core carries 16 of them (7.7 GB/s),
 //      so many more streams than cores (a high --checkers) still progress together.
+// A SHA-1 stream (a wrapped remote whose hash is SHA-1; xs_host_sha1.h) takes tiers 1 and 2 only:
+// the 16-stream engine is MD5's, so past the CPU budget a SHA-1 job is hashed on its caller's thread.
 // A stream submits its jobs one at a time (it waits for job k before submitting job k+1), so its
 // bytes are hashed in order whichever tier takes each job.
 #pragma once
@@ -36,12 +38,19 @@
 #include "md5_x16.h"
 #include "rc_internal.h"
 #include "xs_host_md5.h"
+#include "xs_host_sha1.h"
 
 namespace xs {
 
 class Md5Workers;
 struct Md5Job {
+  // the stream's state, tagged by which pointer is set: st (MD5), or sha (SHA-1) with st == nullptr
   HostMd5* st = nullptr;
+  HostSha1* sha = nullptr;
+  void hash() {  // tiers 1 and 2: the job's bytes into its state, on this thread
+    if (sha) sha->update(p, n);
+    else st->update(p, n);
+  }
   const uint8_t* p = nullptr;
   size_t n = 0;
   std::atomic<int> busy{0};  // 1 from submit until the bytes are hashed (2: a waiter sleeps on it)
@@ -49,6 +58,28 @@ struct Md5Job {
   // multi-buffer engine: the whole blocks left after HostMd5::begin_blocks
   const uint8_t* blk = nullptr;
   size_t nblk = 0;
+};
+
+// One stream's hash state for either type (copyable, like the hashers): what the encrypter's tee
+// and computeHashWithNonce keep per stream and point their jobs at.
+struct HashState {
+  int type = XS_HASH_MD5;
+  HostMd5 md5;
+  HostSha1 sha1;
+  explicit HashState(int t = XS_HASH_MD5) : type(t) {}
+  size_t size() const { return type == XS_HASH_SHA1 ? 20 : 16; }
+  void update(const uint8_t* p, size_t n) {
+    if (type == XS_HASH_SHA1) sha1.update(p, n);
+    else md5.update(p, n);
+  }
+  void final(uint8_t* out) {
+    if (type == XS_HASH_SHA1) sha1.final(out);
+    else md5.final(out);
+  }
+  void bind(Md5Job* j) {  // j hashes into this state
+    j->st = type == XS_HASH_SHA1 ? nullptr : &md5;
+    j->sha = type == XS_HASH_SHA1 ? &sha1 : nullptr;
+  }
 };
 
 // Where jobs went (cumulative, all nodes): scalar workers, callers' threads, engine lanes.
@@ -92,9 +123,9 @@ class Md5Workers {
     }
     // scalar chains already on host cores: busy workers + callers hashing now
     const int on_cores = inline_.load(std::memory_order_relaxed) + busy_workers_.load(std::memory_order_relaxed);
-    if (!lanes_on_ || on_cores < budget_) {
+    if (!lanes_on_ || on_cores < budget_ || j->sha) {  // the x16 lane tier is taken only by MD5 jobs
       inline_.fetch_add(1, std::memory_order_relaxed);
-      j->st->update(j->p, j->n);
+      j->hash();
       inline_.fetch_sub(1, std::memory_order_relaxed);
       md5_tier_stats().inline_++;
       return;
@@ -154,7 +185,7 @@ class Md5Workers {
       busy_workers_.fetch_add(1, std::memory_order_relaxed);
       lk.unlock();
       const auto t0 = std::chrono::steady_clock::now();
-      j->st->update(j->p, j->n);
+      j->hash();
       md5_tier_stats().worker_ns.fetch_add(
           (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(),
           std::memory_order_relaxed);

@@ -23,7 +23,9 @@
 #include <vector>
 
 #include "xs_host_md5.h"
+#include "xs_host_sha1.h"
 #include "xs_internal.h"
+#include "xs_sha1.h"
 #include "xs_topo.h"
 
 namespace xs {
@@ -295,6 +297,62 @@ int xs_md5_batch_dev(const xs_md5_desc* d_desc, uint64_t n, const void* d_src, u
   }
   hipError_t e = launch_md5(d_desc, n, (const uint8_t*)d_src, src_len, d_digest, d_ok, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "md5 launch");
+  return XS_OK;
+}
+
+// ---- hash types (rclone's hash.Type values, fs/hash/hash.go:43)
+size_t xs_hash_size(int type) { return type == XS_HASH_MD5 ? 16 : type == XS_HASH_SHA1 ? 20 : 0; }
+
+// false (with the error set) for anything but XS_HASH_MD5 / XS_HASH_SHA1
+static bool hash_type_ok(int type, const char* who) {
+  if (xs_hash_size(type)) return true;
+  set_error("%s: unknown hash type %d (XS_HASH_MD5 = 1, XS_HASH_SHA1 = 2)", who, type);
+  return false;
+}
+
+static hipError_t launch_hash(int type, const xs_hash_desc* d, uint64_t n, const uint8_t* src, uint64_t src_len,
+                              uint8_t* digest, uint8_t* ok, hipStream_t stream) {
+  return type == XS_HASH_SHA1 ? launch_sha1(d, n, src, src_len, digest, ok, stream)
+                              : launch_md5(d, n, src, src_len, digest, ok, stream);
+}
+
+int xs_hash_batch_dev(int type, const xs_hash_desc* d_desc, uint64_t n, const void* d_src, uint64_t src_len,
+                      uint8_t* d_digest, uint8_t* d_ok, void* stream) {
+  if (!hash_type_ok(type, "xs_hash_batch_dev")) return XS_ERR_INVALID;
+  if (n == 0) return XS_OK;
+  if (!d_desc || !d_digest || (!d_src && src_len) || ((uintptr_t)d_digest & 3u)) {
+    set_error("xs_hash_batch_dev: null argument or digest buffer not 4-byte aligned");
+    return XS_ERR_INVALID;
+  }
+  hipError_t e = launch_hash(type, d_desc, n, (const uint8_t*)d_src, src_len, d_digest, d_ok, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "hash launch");
+  return XS_OK;
+}
+
+// prefix || body on this thread, the host tier's hashers
+static void host_hash(int type, const uint8_t* prefix, size_t prefix_len, const uint8_t* body, uint64_t len,
+                      uint8_t* out) {
+  if (type == XS_HASH_SHA1) {
+    HostSha1 m;
+    m.update(prefix, prefix_len);
+    m.update(body, len);
+    m.final(out);
+  } else {
+    HostMd5 m;
+    if (prefix_len) m.update(prefix, prefix_len);
+    m.update(body, len);
+    m.final(out);
+  }
+}
+
+int xs_host_hash(int type, const void* p, uint64_t n, uint8_t* out) {
+  if (!hash_type_ok(type, "xs_host_hash")) return XS_ERR_INVALID;
+  if (!out || (!p && n)) {
+    set_error("xs_host_hash: null argument");
+    return XS_ERR_INVALID;
+  }
+  static const uint8_t none = 0;
+  host_hash(type, &none, 0, p ? (const uint8_t*)p : &none, n, out);
   return XS_OK;
 }
 
@@ -1230,6 +1288,28 @@ static double lane_md5_bps() {
   return v;
 }
 
+// One GPU lane's SHA-1 rate (xs_sha1.hip), measured with tools/md5_bench.py --hash sha1 at 1 k
+// one-block objects, where one chain per lane sets the time: 65 584 bytes in 1.41 ms (DESIGN.md
+// section 3b, profiles/sha1/md5_bench_sha1.json).  Below MD5's 70 MB/s: 80 rounds and the
+// schedule are ~600 instructions per block against MD5's ~320, and one wave alone on its SIMD is
+// bound by instructions issued.
+constexpr double kLaneSha1Bps = 46e6;
+
+// One host core's SHA-1 rate, measured once at first use (8 MiB, a few ms).
+static double host_sha1_bps() {
+  static const double v = [] {
+    std::vector<uint8_t> b((size_t)8 << 20, 0x5a);
+    uint8_t out[20];
+    const auto t0 = std::chrono::steady_clock::now();
+    HostSha1 m;
+    m.update(b.data(), b.size());
+    m.final(out);
+    const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return s > 0 ? (double)b.size() / s : 500e6;
+  }();
+  return v;
+}
+
 // One host core's MD5 rate, measured once (8 MiB, a few ms).
 static double host_md5_bps() {
   static const double v = [] {
@@ -1255,13 +1335,14 @@ static int host_md5_threads_default() {
 // Below this an object stays on its GPU lane: a 16 MiB lane takes ~0.24 s, longer than a 4 GiB
 // group's PCIe copies; shorter objects finish within the group's own copy time, and hashing them on
 // host cores only competes with the file reads feeding the next group (configs[4]'s 4 KiB-8 MiB
-// tree measured no gain, profiles/r02/e2e_routing_ab.jsonl).
+// tree measured no gain, profiles/r02/e2e_routing_ab.jsonl).  SHA-1 keeps the floor: at its 46 MB/s
+// lane the same 0.24 s is ~11 MiB, too close to 16 to justify a second threshold.
 constexpr uint64_t kHostMd5Min = 16ull << 20;
 
 // Which objects of a group go to the host (route[k] = 1): take the longest first while the host
 // pool's makespan stays below that object's GPU lane time, i.e. while moving it shortens the
 // group (the group's GPU MD5 time is then set by the longest object left on the GPU).
-static void route_host_md5(const uint64_t* wire_len, size_t n, int threads, std::vector<uint8_t>& route) {
+static void route_host_md5(int type, const uint64_t* wire_len, size_t n, int threads, std::vector<uint8_t>& route) {
   route.assign(n, 0);
   if (threads <= 0 || n == 0) return;
   std::vector<size_t> order;
@@ -1269,7 +1350,8 @@ static void route_host_md5(const uint64_t* wire_len, size_t n, int threads, std:
     if (wire_len[k] >= kHostMd5Min) order.push_back(k);
   if (order.empty()) return;
   std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return wire_len[a] > wire_len[b]; });
-  const double hb = host_md5_bps(), lb = lane_md5_bps();
+  const bool sha1 = type == XS_HASH_SHA1;  // the rate overrides (XS_MD5_*_BPS) are MD5-only
+  const double hb = sha1 ? host_sha1_bps() : host_md5_bps(), lb = sha1 ? kLaneSha1Bps : lane_md5_bps();
   double sum = 0, mx = 0;
   for (size_t k : order) {
     const double L = (double)wire_len[k];
@@ -1300,6 +1382,7 @@ struct HostMd5Pool {
   uint64_t bytes = 0, count = 0;
   int pending[2] = {0, 0};  // unfinished jobs per staging buffer
   int node = -1;            // the engine's NUMA node: workers run on its CPUs
+  int type = XS_HASH_MD5;   // every job of a pool has the call's hash type
 
   void push(const Job& j, int max_threads) {
     std::lock_guard<std::mutex> g(mu);
@@ -1321,10 +1404,7 @@ struct HostMd5Pool {
       if (next >= jobs.size()) return;
       const Job j = jobs[next++];
       lk.unlock();
-      HostMd5 m;
-      m.update(j.prefix, 32);
-      m.update(j.body, j.len);
-      m.final(j.out);
+      host_hash(type, j.prefix, 32, j.body, j.len, j.out);
       lk.lock();
       if (j.tag >= 0 && --pending[j.tag] == 0) idle.notify_all();
     }
@@ -1350,10 +1430,12 @@ struct HostMd5Pool {
 // Seal + MD5 of whole objects in groups of ~budget plaintext bytes; with `body` the wire
 // bodies also come back (packed: object i at xs_put_body_offset of i, one D2H per group).
 // host_threads > 0 lets the longest objects of a group be hashed on the host (route_host_md5).
-static int seal_md5_impl(xs_engine* e, const uint8_t key[32], uint64_t nobj, const uint8_t* nonces,
+static int seal_md5_impl(xs_engine* e, int type, const uint8_t key[32], uint64_t nobj, const uint8_t* nonces,
                          const uint64_t* offs, const uint64_t* lens, const void* plain, uint8_t* md5,
                          uint8_t* body, int host_threads, uint64_t* host_routed) {
   if (host_routed) *host_routed = 0;
+  if (!hash_type_ok(type, "xs_engine_seal_hash")) return XS_ERR_INVALID;
+  const size_t hs = xs_hash_size(type);  // digest stride: md5[hs * i]
   if (nobj == 0) return XS_OK;
   if (!e || !key || !nonces || !offs || !lens || !md5) {
     set_error("xs_engine_seal_md5: null argument");
@@ -1373,6 +1455,7 @@ static int seal_md5_impl(xs_engine* e, const uint8_t key[32], uint64_t nobj, con
   auto& hb = e->hb;
   HostMd5Pool host;  // joined (every digest written) before this function returns
   host.node = e->numa;
+  host.type = type;
   // groups of whole objects, ~budget plaintext bytes each (MD5 is sequential per object)
   // large groups: the MD5 of a group takes as long as its largest object (one lane each)
   const uint64_t budget = std::max<uint64_t>((uint64_t)e->batch * XS_BLOCK_DATA * 16, 4096ull << 20);
@@ -1395,7 +1478,7 @@ static int seal_md5_impl(xs_engine* e, const uint8_t key[32], uint64_t nobj, con
     const uint64_t span = hi > lo ? hi - lo : 0, ng = o1 - o0;
     wlen.resize(ng);
     for (uint64_t i = o0; i < o1; i++) wlen[i - o0] = body_bytes(lens[i]);
-    route_host_md5(wlen.data(), ng, host_threads, route);
+    route_host_md5(type, wlen.data(), ng, host_threads, route);
     desc.clear();
     mdesc.clear();
     gpu_obj.clear();
@@ -1433,7 +1516,7 @@ static int seal_md5_impl(xs_engine* e, const uint8_t key[32], uint64_t nobj, con
     if (!grow(&hb.d_plain, &hb.plain_cap, span) || !grow(&hb.d_body, &hb.body_cap, bsum) ||
         !grow(&hb.d_desc, &hb.desc_cap, nblk * sizeof(xs_block_desc)) ||
         !grow(&hb.d_mdesc, &hb.mdesc_cap, std::max<uint64_t>(ngpu, 1) * sizeof(xs_md5_desc)) ||
-        !grow(&hb.d_digest, &hb.digest_cap, std::max<uint64_t>(ngpu, 1) * 16) ||
+        !grow(&hb.d_digest, &hb.digest_cap, std::max<uint64_t>(ngpu, 1) * hs) ||
         !grow((uint8_t**)&hb.d_keys, &hb.keys_cap, nblk * sizeof(BlockKey))) {
       set_error("xs_engine_seal_md5: device allocation failed");
       return XS_ERR_HIP;
@@ -1481,10 +1564,10 @@ static int seal_md5_impl(xs_engine* e, const uint8_t key[32], uint64_t nobj, con
     }
     if (err != hipSuccess) return hip_fail(err, "D2H");
     if (ngpu) {
-      err = launch_md5((const xs_md5_desc*)hb.d_mdesc, ngpu, hb.d_body, bsum, hb.d_digest, nullptr, st);
+      err = launch_hash(type, (const xs_md5_desc*)hb.d_mdesc, ngpu, hb.d_body, bsum, hb.d_digest, nullptr, st);
       if (err != hipSuccess) return hip_fail(err, "md5");
-      dig.resize(16 * ngpu);
-      err = hipMemcpyAsync(dig.data(), hb.d_digest, ngpu * 16, hipMemcpyDeviceToHost, st);
+      dig.resize(hs * ngpu);
+      err = hipMemcpyAsync(dig.data(), hb.d_digest, ngpu * hs, hipMemcpyDeviceToHost, st);
       if (err != hipSuccess) return hip_fail(err, "D2H");
     }
     err = hipStreamSynchronize(ax);
@@ -1496,14 +1579,14 @@ static int seal_md5_impl(xs_engine* e, const uint8_t key[32], uint64_t nobj, con
       memcpy(j.prefix + 8, nonces + 24 * i, 24);
       j.body = body ? body + body_pos + wpos[i - o0] : hb.route[tag] + spos[k];
       j.len = wlen[i - o0];
-      j.out = md5 + 16 * i;
+      j.out = md5 + hs * i;
       j.tag = body ? -1 : tag;
       host.push(j, host_threads);
     }
     // the host-side descriptor vectors are reused next group: wait for this group's copies
     err = hipStreamSynchronize(st);
     if (err != hipSuccess) return hip_fail(err, "engine stream");
-    for (uint64_t k = 0; k < ngpu; k++) memcpy(md5 + 16 * gpu_obj[k], dig.data() + 16 * k, 16);
+    for (uint64_t k = 0; k < ngpu; k++) memcpy(md5 + hs * gpu_obj[k], dig.data() + hs * k, hs);
     body_pos += w;
     o0 = o1;
   }
@@ -1521,7 +1604,19 @@ extern "C" int xs_engine_seal_md5(xs_engine* e, const uint8_t key[32], uint64_t 
     set_error("xs_engine_seal_md5: null engine");
     return XS_ERR_INVALID;
   }
-  return seal_md5_impl(e, key, nobj, nonces, offs, lens, plain, md5, nullptr,
+  return seal_md5_impl(e, XS_HASH_MD5, key, nobj, nonces, offs, lens, plain, md5, nullptr,
+                       e->host_md5_threads >= 0 ? e->host_md5_threads : host_md5_threads_default(), nullptr);
+}
+
+extern "C" int xs_engine_seal_hash(xs_engine* e, int type, const uint8_t key[32], uint64_t nobj,
+                                   const uint8_t* nonces, const uint64_t* offs, const uint64_t* lens,
+                                   const void* plain, uint8_t* digest) {
+  if (!hash_type_ok(type, "xs_engine_seal_hash")) return XS_ERR_INVALID;
+  if (!e) {
+    set_error("xs_engine_seal_hash: null engine");
+    return XS_ERR_INVALID;
+  }
+  return seal_md5_impl(e, type, key, nobj, nonces, offs, lens, plain, digest, nullptr,
                        e->host_md5_threads >= 0 ? e->host_md5_threads : host_md5_threads_default(), nullptr);
 }
 
@@ -1542,7 +1637,23 @@ extern "C" int xs_engine_put_batch(xs_engine* e, const uint8_t key[32], uint64_t
     set_error("xs_engine_put_batch: null engine");
     return XS_ERR_INVALID;
   }
-  return seal_md5_impl(e, key, nobj, nonces, offs, lens, plain, md5, (uint8_t*)body,
+  return seal_md5_impl(e, XS_HASH_MD5, key, nobj, nonces, offs, lens, plain, md5, (uint8_t*)body,
+                       e->host_md5_threads >= 0 ? e->host_md5_threads : host_md5_threads_default(), nullptr);
+}
+
+extern "C" int xs_engine_put_batch_hash(xs_engine* e, int type, const uint8_t key[32], uint64_t nobj,
+                                        const uint8_t* nonces, const uint64_t* offs, const uint64_t* lens,
+                                        const void* plain, void* body, uint8_t* digest) {
+  if (!hash_type_ok(type, "xs_engine_put_batch_hash")) return XS_ERR_INVALID;
+  if (nobj && !body) {
+    set_error("xs_engine_put_batch_hash: null body");
+    return XS_ERR_INVALID;
+  }
+  if (!e) {
+    set_error("xs_engine_put_batch_hash: null engine");
+    return XS_ERR_INVALID;
+  }
+  return seal_md5_impl(e, type, key, nobj, nonces, offs, lens, plain, digest, (uint8_t*)body,
                        e->host_md5_threads >= 0 ? e->host_md5_threads : host_md5_threads_default(), nullptr);
 }
 
@@ -1634,8 +1745,10 @@ extern "C" xs_engine* xs_pool_next(xs_pool* p) {
 
 // Objects [0, nobj) split into k contiguous ranges of about equal plaintext bytes, one engine
 // each, run on their own threads; the first failure's message is passed to the caller's thread.
-static int pool_seal_md5(xs_pool* p, const uint8_t key[32], uint64_t nobj, const uint8_t* nonces,
+static int pool_seal_md5(xs_pool* p, int type, const uint8_t key[32], uint64_t nobj, const uint8_t* nonces,
                          const uint64_t* offs, const uint64_t* lens, const void* plain, uint8_t* md5, uint8_t* body) {
+  if (!hash_type_ok(type, "xs_pool_seal_hash")) return XS_ERR_INVALID;
+  const size_t hs = xs_hash_size(type);
   if (!p || p->engines.empty()) {
     set_error("xs_pool: no engines");
     return XS_ERR_INVALID;
@@ -1669,7 +1782,7 @@ static int pool_seal_md5(xs_pool* p, const uint8_t key[32], uint64_t nobj, const
     xs_engine* e = p->engines[(first + r) % p->engines.size()];
     th.emplace_back([&, r, a, b, rb, e] {
       pin_thread_to_node(e->numa);
-      rc[r] = seal_md5_impl(e, key, b - a, nonces + 24 * a, offs + a, lens + a, plain, md5 + 16 * a, rb,
+      rc[r] = seal_md5_impl(e, type, key, b - a, nonces + 24 * a, offs + a, lens + a, plain, md5 + hs * a, rb,
                             e->host_md5_threads >= 0 ? e->host_md5_threads : per, nullptr);
       if (rc[r] != XS_OK) msg[r] = xs_last_error();
     });
@@ -1685,7 +1798,12 @@ static int pool_seal_md5(xs_pool* p, const uint8_t key[32], uint64_t nobj, const
 
 extern "C" int xs_pool_seal_md5(xs_pool* p, const uint8_t key[32], uint64_t nobj, const uint8_t* nonces,
                                 const uint64_t* offs, const uint64_t* lens, const void* plain, uint8_t* md5) {
-  return pool_seal_md5(p, key, nobj, nonces, offs, lens, plain, md5, nullptr);
+  return pool_seal_md5(p, XS_HASH_MD5, key, nobj, nonces, offs, lens, plain, md5, nullptr);
+}
+
+extern "C" int xs_pool_seal_hash(xs_pool* p, int type, const uint8_t key[32], uint64_t nobj, const uint8_t* nonces,
+                                 const uint64_t* offs, const uint64_t* lens, const void* plain, uint8_t* digest) {
+  return pool_seal_md5(p, type, key, nobj, nonces, offs, lens, plain, digest, nullptr);
 }
 
 extern "C" int xs_pool_put_batch(xs_pool* p, const uint8_t key[32], uint64_t nobj, const uint8_t* nonces,
@@ -1695,5 +1813,16 @@ extern "C" int xs_pool_put_batch(xs_pool* p, const uint8_t key[32], uint64_t nob
     set_error("xs_pool_put_batch: null body");
     return XS_ERR_INVALID;
   }
-  return pool_seal_md5(p, key, nobj, nonces, offs, lens, plain, md5, (uint8_t*)body);
+  return pool_seal_md5(p, XS_HASH_MD5, key, nobj, nonces, offs, lens, plain, md5, (uint8_t*)body);
+}
+
+extern "C" int xs_pool_put_batch_hash(xs_pool* p, int type, const uint8_t key[32], uint64_t nobj,
+                                      const uint8_t* nonces, const uint64_t* offs, const uint64_t* lens,
+                                      const void* plain, void* body, uint8_t* digest) {
+  if (!hash_type_ok(type, "xs_pool_put_batch_hash")) return XS_ERR_INVALID;
+  if (nobj && !body) {
+    set_error("xs_pool_put_batch_hash: null body");
+    return XS_ERR_INVALID;
+  }
+  return pool_seal_md5(p, type, key, nobj, nonces, offs, lens, plain, digest, (uint8_t*)body);
 }

@@ -191,3 +191,32 @@ def md5_batch(desc, src: torch.Tensor):
                                      _stream(src))
     _lib.check(rc, "xs_md5_batch_dev")
     return dig[:n * 16].view(-1, 16), ok[:n]
+
+
+HASH_MD5, HASH_SHA1 = 1, 2  # XS_HASH_* (rclone's hash.Type values)
+HASH_DESC_BYTES = MD5_DESC_BYTES
+
+
+def hash_batch(hash_type, desc, src: torch.Tensor):
+    """MD5 or SHA-1 of many streams in HBM (xs_hash_batch_dev): hash_type "md5" / "sha1" (or
+    HASH_MD5 / HASH_SHA1), desc as for md5_batch; returns (digests uint8 [n, 16 or 20], ok uint8
+    [n]) on the device."""
+    ht = {"md5": HASH_MD5, "sha1": HASH_SHA1}.get(hash_type, hash_type)
+    hs = _lib.lib().xs_hash_size(ht) if isinstance(ht, int) else 0
+    if hs == 0:
+        raise ValueError(f"unsupported hash type {hash_type!r} (md5, sha1)")
+    _require_gpu(src)
+    if isinstance(desc, torch.Tensor):
+        _require_gpu(desc)
+        d = desc
+    else:
+        import numpy as np
+        assert desc.dtype.itemsize == HASH_DESC_BYTES
+        d = torch.from_numpy(np.frombuffer(desc.tobytes(), dtype=np.uint8).copy()).to(src.device)
+    n = d.numel() // HASH_DESC_BYTES
+    dig = torch.empty(max(n, 1) * hs, dtype=torch.uint8, device=src.device)
+    ok = torch.empty(max(n, 1), dtype=torch.uint8, device=src.device)
+    rc = _lib.lib().xs_hash_batch_dev(ht, d.data_ptr(), n, src.data_ptr(), src.numel(), dig.data_ptr(), ok.data_ptr(),
+                                      _stream(src))
+    _lib.check(rc, "xs_hash_batch_dev")
+    return dig[:n * hs].view(-1, hs), ok[:n]
