@@ -149,22 +149,37 @@ int xs_md5_batch_dev(const xs_md5_desc *d_desc, uint64_t n, const void *d_src, u
 /* Hash types.  Fs.put and cryptcheck hash the ciphertext with the wrapped remote's
  * Hashes().GetOne() (crypt.go:516, cmd/cryptcheck/cryptcheck.go:74-79): MD5 where the remote has
  * it, SHA-1 for Backblaze B2, Box and the other SHA-1-only remotes (fs/hash/hash.go:123-127).  The
- * values are rclone's own hash.Type values (1 << registration index, fs/hash/hash.go:43), so a
- * binding passes its hashType through.  Every *_hash / *_type entry point below is the MD5 entry
- * point of the same name with the type added; any other type is XS_ERR_INVALID / RC_ERR_INVALID
- * with a message in xs_last_error, and nothing is launched. */
+ * values of these two are rclone's own hash.Type values (1 << registration index,
+ * fs/hash/hash.go:43), so a binding passes its hashType through.  Every *_hash / *_type entry point
+ * below is the MD5 entry point of the same name with the type added; any other type is
+ * XS_ERR_INVALID / RC_ERR_INVALID with a message in xs_last_error, and nothing is launched.
+ *
+ * XS_HASH_QUICKXOR is QuickXorHash (backend/onedrive/quickxorhash), the only hash OneDrive
+ * Personal, Business and SharePoint offer (backend/onedrive/onedrive.go:113, :344-351).  rclone
+ * gives "quickxor" its hash.Type when the onedrive backend registers it (1 << the number of types
+ * registered so far), so that value depends on import order and is NOT passed through:
+ * XS_HASH_QUICKXOR is a fixed value of this library's own, and a binding maps by name
+ * (hash.Type.String() == "quickxor"). */
 #define XS_HASH_MD5 1
 #define XS_HASH_SHA1 2
+#define XS_HASH_QUICKXOR 0x40000000
 typedef xs_md5_desc xs_hash_desc;
-/* Digest bytes of a hash type: 16, 20, or 0 for an unknown type. */
+/* Digest bytes of a hash type: 16 (MD5), 20 (SHA-1, QuickXorHash), or 0 for an unknown type. */
 size_t xs_hash_size(int type);
-/* xs_md5_batch_dev for either type: d_digest[xs_hash_size(type)*i] = H(prefix_i || src[off_i :
- * off_i+len_i]), SHA-1 digests in FIPS 180-4 byte order.  d_digest must be 4-byte aligned. */
+/* xs_md5_batch_dev for any type: d_digest[xs_hash_size(type)*i] = H(prefix_i || src[off_i :
+ * off_i+len_i]), SHA-1 digests in FIPS 180-4 byte order, QuickXorHash digests as quickxorhash.go's
+ * Sum writes them.  d_digest must be 4-byte aligned.  MD5 and SHA-1 run one lane per object;
+ * QuickXorHash splits every object over many workgroups (xs_quickxor_slice() bytes per step), so
+ * one long object uses the whole device; its d_digest is zeroed on `stream` first and an invalid
+ * descriptor's digest stays zero. */
 int xs_hash_batch_dev(int type, const xs_hash_desc *d_desc, uint64_t n, const void *d_src, uint64_t src_len,
                       uint8_t *d_digest, uint8_t *d_ok, void *stream);
 /* One-shot digest of p[0:n] on the calling thread: what the host tier computes for the objects
  * routed off the GPU lanes.  Needs no GPU. */
 int xs_host_hash(int type, const void *p, uint64_t n, uint8_t *out);
+/* Bytes of one object that a workgroup of the QuickXorHash kernel takes per step (a multiple of
+ * 160): the lengths at which the kernel's paths change, for tests. */
+uint64_t xs_quickxor_slice(void);
 
 /* Host-memory engine: pinned staging, per-slot streams, H2D/kernel/D2H overlapped. */
 typedef struct xs_engine xs_engine;
@@ -208,7 +223,9 @@ int xs_engine_put_batch(xs_engine *e, const uint8_t key[32], uint64_t nobj, cons
 uint64_t xs_put_body_bytes(uint64_t nobj, const uint64_t *lens);
 /* xs_engine_seal_md5 / xs_engine_put_batch with the wrapped remote's hash type: digest is packed at
  * stride xs_hash_size(type).  Routing of long objects to host cores works as for MD5, with the
- * SHA-1 lane and host rates (xs_engine_set_host_md5 and xs_engine_md5_stats cover either type). */
+ * SHA-1 lane and host rates (xs_engine_set_host_md5 and xs_engine_md5_stats cover either type).
+ * XS_HASH_QUICKXOR routes nothing to the host (xs_engine_md5_stats counts 0 routed): its kernel
+ * splits one object over the whole device. */
 int xs_engine_seal_hash(xs_engine *e, int type, const uint8_t key[32], uint64_t nobj, const uint8_t *nonces,
                         const uint64_t *offs, const uint64_t *lens, const void *plain, uint8_t *digest);
 int xs_engine_put_batch_hash(xs_engine *e, int type, const uint8_t key[32], uint64_t nobj, const uint8_t *nonces,
@@ -367,8 +384,9 @@ void rc_encrypter_nonce(const rc_encrypter *e, uint8_t out[24]);
  * far -- what hasher.Sums() gives after the wrapped Put -- or RC_ERR_INVALID if the option is off. */
 int32_t rc_encrypter_set_md5(rc_encrypter *e, int32_t on);
 int32_t rc_encrypter_md5(rc_encrypter *e, uint8_t out[16]);
-/* The same tee with the wrapped remote's hash type (XS_HASH_MD5 / XS_HASH_SHA1; 0 turns the hash
- * off; any other value is RC_ERR_INVALID), before the first read only.  One type per encrypter: a
+/* The same tee with the wrapped remote's hash type (XS_HASH_MD5 / XS_HASH_SHA1 /
+ * XS_HASH_QUICKXOR; 0 turns the hash off; any other value is RC_ERR_INVALID), before the first
+ * read only.  One type per encrypter: a
  * second call replaces the first.  rc_encrypter_hash writes the xs_hash_size(type)-byte digest of
  * exactly the bytes returned so far; RC_ERR_INVALID if the hash is off or cap is too small.
  * rc_encrypter_set_md5(e, on) / rc_encrypter_md5 are the MD5 case of these two. */

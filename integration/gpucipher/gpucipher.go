@@ -273,12 +273,33 @@ func New(dataKey, nameKey *[32]byte, nameTweak *[16]byte, passBadBlocks bool) (*
 	return c, nil
 }
 
-// HashMD5 and HashSHA1 are the hash types the library computes: rclone's own hash.MD5 and hash.SHA1
-// values (fs/hash/hash.go:43), so backend/crypt passes int32(hashType) through.
+// HashMD5, HashSHA1 and HashQuickXor are the hash types the library computes.  The first two are
+// rclone's own hash.MD5 and hash.SHA1 values (fs/hash/hash.go:43).  HashQuickXor is OneDrive's
+// QuickXorHash: rclone gives "quickxor" its hash.Type when backend/onedrive registers it
+// (onedrive.go:113), so that value depends on import order, and HashQuickXor is a fixed value of
+// the library's own.  backend/crypt therefore maps its hashType with HashTypeByName and never
+// passes the number through.
 const (
-	HashMD5  int32 = C.XS_HASH_MD5
-	HashSHA1 int32 = C.XS_HASH_SHA1
+	HashMD5      int32 = C.XS_HASH_MD5
+	HashSHA1     int32 = C.XS_HASH_SHA1
+	HashQuickXor int32 = C.XS_HASH_QUICKXOR
 )
+
+// HashTypeByName maps a hash.Type's String() ("md5", "sha1", "quickxor") to the library's type;
+// ok is false for any other hash (the caller keeps the reference's Go path).  In backend/crypt:
+//
+//	gpuType, ok := gpucipher.HashTypeByName(hashType.String())
+func HashTypeByName(name string) (hashType int32, ok bool) {
+	switch name {
+	case "md5":
+		return HashMD5, true
+	case "sha1":
+		return HashSHA1, true
+	case "quickxor":
+		return HashQuickXor, true
+	}
+	return 0, false
+}
 
 // ComputeHashWithNonce is ComputeHashWithNonceType for MD5.
 func (c *Cipher) ComputeHashWithNonce(nonce *[24]byte, in io.Reader) (hashStr string, err error) {
@@ -286,15 +307,16 @@ func (c *Cipher) ComputeHashWithNonce(nonce *[24]byte, in io.Reader) (hashStr st
 }
 
 // ComputeHashWithNonceType is computeHashWithNonce (crypt.go:784-806) after src.Open, for the
-// wrapped remote's hash type (MD5, or SHA-1 for Backblaze B2, Box and the like): in is
+// wrapped remote's hash type (MD5, SHA-1 for Backblaze B2, Box and the like, QuickXorHash for
+// OneDrive): in is
 // read to EOF, sealed with nonce on the GPU -- concurrent checkers' seals share launches -- and
 // "RCLONE\0\0" || nonce || wire blocks is hashed on host cores; in is closed when it is an
 // io.Closer (the library does what `defer fs.CheckClose(in, &err)` does).  It returns what the
 // reference returns from that point: ("", "failed to hash data: %w") for a read error, the hex
 // digest and nil, or the hex digest with the close error.  crypt.go's change, after src.Open:
 //
-//	if f.cipher.gpu != nil && (hashType == hash.MD5 || hashType == hash.SHA1) {
-//		return f.cipher.gpu.ComputeHashWithNonceType(int32(hashType), (*[24]byte)(&nonce), in)
+//	if gpuType, ok := gpucipher.HashTypeByName(hashType.String()); ok && f.cipher.gpu != nil {
+//		return f.cipher.gpu.ComputeHashWithNonceType(gpuType, (*[24]byte)(&nonce), in)
 //	}
 //	defer fs.CheckClose(in, &err) // the Go path, unchanged
 func (c *Cipher) ComputeHashWithNonceType(hashType int32, nonce *[24]byte, in io.Reader) (hashStr string, err error) {
@@ -381,7 +403,7 @@ func (fh *Encrypter) MD5() (sum [16]byte, err error) {
 	return sum, nil
 }
 
-// SetHash is SetMD5 for the wrapped remote's hash type (HashMD5, HashSHA1); put uses Hash() as
+// SetHash is SetMD5 for the wrapped remote's hash type (HashMD5, HashSHA1, HashQuickXor); put uses Hash() as
 // srcHash.
 func (fh *Encrypter) SetHash(hashType int32) error {
 	rc := C.rc_encrypter_set_hash(fh.h, C.int32_t(hashType))
@@ -582,7 +604,7 @@ func (c *Cipher) HashBatchWithNonce(nonces [][24]byte, srcs []io.ReadCloser) (su
 }
 
 // HashBatchWithNonceType is HashBatchWithNonce for the wrapped remote's hash type (HashMD5,
-// HashSHA1): sums[i] holds 16 or 20 bytes.
+// HashSHA1, HashQuickXor): sums[i] holds 16 or 20 bytes.
 func (c *Cipher) HashBatchWithNonceType(hashType int32, nonces [][24]byte, srcs []io.ReadCloser) (sums [][]byte, errs []error, err error) {
 	size := int(C.xs_hash_size(C.int(hashType)))
 	if size == 0 {

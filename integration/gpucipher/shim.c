@@ -70,7 +70,8 @@ int32_t gpucipher_hash_batch(rc_cipher *c, uint64_t n, const uintptr_t *srcs, ui
 }
 
 /* The two calls above for the wrapped remote's hash type (XS_HASH_MD5 / XS_HASH_SHA1 = rclone's
- * hash.MD5 / hash.SHA1 values): digest holds xs_hash_size(type) bytes per object. */
+ * hash.MD5 / hash.SHA1 values; XS_HASH_QUICKXOR, the library's own value, which the Go half maps
+ * from hash.Type.String() == "quickxor"): digest holds xs_hash_size(type) bytes per object. */
 int32_t gpucipher_compute_hash_type(rc_cipher *c, int32_t type, uintptr_t src, int closer, const uint8_t *nonce,
                                     uint8_t *digest) {
   return rc_compute_hash_with_nonce_type(c, type, gpucipher_reader(src, closer, 0), nonce, digest);

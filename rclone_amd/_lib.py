@@ -62,6 +62,7 @@ _SIGS = [
     ("xs_hash_size", ctypes.c_size_t, [ctypes.c_int]),
     ("xs_hash_batch_dev", ctypes.c_int, [ctypes.c_int, vp, u64, vp, u64, vp, vp, vp]),
     ("xs_host_hash", ctypes.c_int, [ctypes.c_int, vp, u64, vp]),
+    ("xs_quickxor_slice", u64, []),
     ("xs_clock_probe_dev", ctypes.c_int, [vp, vp, ctypes.c_double, vp]),
     ("xs_engine_create", vp, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int]),
     ("xs_engine_destroy", None, [vp]),

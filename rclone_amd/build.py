@@ -34,7 +34,7 @@ HEADER = os.path.join(ROOT, "include", "rclone_crypt_gpu.h")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("RCLONE_AMD_ARCH", "gfx950")
 
-SOURCES = ["xs_kernels.hip", "xs_md5.hip", "xs_sha1.hip", "xs_eme.hip", "xs_probe.hip", "xs_api.cpp", "xs_topo.cpp", "cipher.cpp", "names.cpp",
+SOURCES = ["xs_kernels.hip", "xs_md5.hip", "xs_sha1.hip", "xs_quickxor.hip", "xs_eme.hip", "xs_probe.hip", "xs_api.cpp", "xs_topo.cpp", "cipher.cpp", "names.cpp",
            "names_gpu.cpp", "scrypt.cpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-result"]
 BUILD_ID_TAG = b"xs-build-id:"

@@ -39,17 +39,19 @@ FILE_MAGIC = b"RCLONE\x00\x00"
 RC_NIL, RC_EOF, RC_UNEXPECTED_EOF, RC_USER_BASE = 0, 1, 2, 16
 
 # hash types of the ciphertext hash: rclone's hash.Type values (fs/hash/hash.go:43), XS_HASH_* of
-# include/rclone_crypt_gpu.h
-HASH_MD5, HASH_SHA1 = 1, 2
-HASH_TYPES = {"md5": HASH_MD5, "sha1": HASH_SHA1}
-HASH_SIZES = {HASH_MD5: 16, HASH_SHA1: 20}
+# include/rclone_crypt_gpu.h.  "quickxor" (OneDrive's QuickXorHash) gets its hash.Type when the
+# onedrive backend registers it, so it is mapped by name to a fixed value of the library's own.
+HASH_MD5, HASH_SHA1, HASH_QUICKXOR = 1, 2, 0x40000000
+HASH_TYPES = {"md5": HASH_MD5, "sha1": HASH_SHA1, "quickxor": HASH_QUICKXOR}
+HASH_SIZES = {HASH_MD5: 16, HASH_SHA1: 20, HASH_QUICKXOR: 20}
 
 
 def hash_type_id(name) -> int:
-    """"md5" / "sha1" (hash.Type.String()) or the numeric type -> XS_HASH_*; ValueError otherwise."""
+    """"md5" / "sha1" / "quickxor" (hash.Type.String()) or the numeric type -> XS_HASH_*; ValueError
+    otherwise."""
     ht = HASH_TYPES.get(name, name)
     if ht not in HASH_SIZES:
-        raise ValueError(f"unsupported hash type {name!r} (md5, sha1)")
+        raise ValueError(f"unsupported hash type {name!r} (md5, sha1, quickxor)")
     return ht
 
 
@@ -365,7 +367,7 @@ class Cipher(NameCipherMixin):
     def hash_batch_with_nonce(self, items, hash_type="md5"):
         """Fs.computeHashWithNonce (crypt.go:784), batched: items = [(nonce, src)], src a
         Go-style reader (closed after reading, fs.CheckClose).  hash_type is the wrapped remote's
-        Hashes().GetOne(): "md5" or "sha1".  Sealing and hashing both run on the GPU
+        Hashes().GetOne(): "md5", "sha1" or "quickxor".  Sealing and hashing both run on the GPU
         (rc_hash_batch_with_nonce_type); returns per item the 16- or 20-byte digest, or the
         exception the source raised (the reference wraps it: "failed to hash data: %w")."""
         ht = hash_type_id(hash_type)
@@ -390,7 +392,7 @@ class Cipher(NameCipherMixin):
         return out
 
     def compute_hash_with_nonce(self, nonce: bytes, src, hash_type="md5") -> str:
-        """computeHashWithNonce (crypt.go:784): hex digest (hash_type "md5" or "sha1") of src
+        """computeHashWithNonce (crypt.go:784): hex digest (hash_type "md5", "sha1" or "quickxor") of src
         encrypted with nonce, one object per call (rc_compute_hash_with_nonce[_type]: GPU seal,
         group-committed with concurrent callers; the hash on host cores).  src is closed if it has
         close() (fs.CheckClose); its error is raised."""
@@ -492,7 +494,7 @@ class Encrypter:
         return d.raw
 
     def set_hash(self, name):
-        """The tee hash with the wrapped remote's hash type: "md5", "sha1", or None to turn it off
+        """The tee hash with the wrapped remote's hash type: "md5", "sha1", "quickxor", or None to turn it off
         (rc_encrypter_set_hash); before the first read only."""
         ht = hash_type_id(name) if name is not None else 0
         _raise(_lib.lib().rc_encrypter_set_hash(self._h, ht))

@@ -14,14 +14,16 @@ a13-a16), on top of the GPU cipher (rclone_amd.crypt -> librclone_crypt.so):
 
 ``MemoryRemote`` is the minimal backend/memory the tests and tools wrap (memory.go:580-646:
 MD5 hash computed on demand, Open honouring Range/Seek); ``MemoryRemote(hash_type="sha1")`` stands
-for a remote whose only hash is SHA-1 (Backblaze B2, Box).  The overlay hashes the ciphertext with
+for a remote whose only hash is SHA-1 (Backblaze B2, Box) and ``MemoryRemote(hash_type="quickxor")``
+for OneDrive, whose only hash is QuickXorHash.  The overlay hashes the ciphertext with
 the wrapped remote's ``Hashes().GetOne()`` (crypt.go:516, cryptcheck.go:74-79): MD5 where the remote
-has it, else SHA-1.  File names use crypt's "off" name
+has it, else SHA-1, else QuickXorHash.  File names use crypt's "off" name
 mode (cipher.go:529: remote + ".bin"); name encryption itself is out of scope.
 """
+import ctypes
 import hashlib
 
-from . import crypt
+from . import _lib, crypt
 from .crypt import EOF, CryptError
 
 SUFFIX = ".bin"  # encryptedSuffix, cipher.go:193
@@ -65,13 +67,24 @@ class _BytesReader:
         pass
 
 
+def _hexdigest(hash_type: str, data: bytes) -> str:
+    """Hex digest of a stored object.  hashlib has no QuickXorHash: that one goes through the
+    library's host hasher (xs_host_hash)."""
+    if hash_type != "quickxor":
+        return hashlib.new(hash_type, data).hexdigest()
+    out = ctypes.create_string_buffer(20)
+    _lib.check(_lib.lib().xs_host_hash(crypt.HASH_QUICKXOR, bytes(data), len(data), out), "xs_host_hash")
+    return out.raw.hex()
+
+
 class MemoryRemote:
     """Minimal backend/memory: objects are byte strings; `hashes` is the set of supported hash
-    types (Fs.Hashes()): MD5 as backend/memory, or SHA-1 alone as Backblaze B2 and Box."""
+    types (Fs.Hashes()): MD5 as backend/memory, SHA-1 alone as Backblaze B2 and Box, or QuickXorHash
+    alone as OneDrive."""
 
     def __init__(self, hash_type: str = "md5"):
         if hash_type not in crypt.HASH_TYPES:
-            raise ValueError(f"unsupported hash type {hash_type!r} (md5, sha1)")
+            raise ValueError(f"unsupported hash type {hash_type!r} (md5, sha1, quickxor)")
         self.hashes = (hash_type,)
         self.objects = {}
         self._hash = {}
@@ -107,7 +120,7 @@ class MemoryRemote:
 
     def hash(self, remote: str) -> str:
         if remote not in self._hash:
-            self._hash[remote] = hashlib.new(self.hashes[0], self.objects[remote]).hexdigest()
+            self._hash[remote] = _hexdigest(self.hashes[0], self.objects[remote])
         return self._hash[remote]
 
     def size(self, remote: str) -> int:
@@ -150,21 +163,24 @@ class CryptFs:
 
     def hash_type(self) -> str:
         """f.Fs.Hashes().GetOne() (fs/hash/hash.go:123-127: the lowest registered type the remote
-        supports): "md5" if the wrapped remote has it, else "sha1".  A remote without a `hashes`
+        supports): "md5" if the wrapped remote has it, else "sha1", else "quickxor" (registered by
+        the onedrive backend, after the built-in types).  A remote without a `hashes`
         attribute is taken to be MD5's, as before."""
         hashes = getattr(self.wrapped, "hashes", ("md5",))
-        for ht in ("md5", "sha1"):
+        for ht in ("md5", "sha1", "quickxor"):
             if ht in hashes:
                 return ht
-        raise CryptError(f"wrapped remote supports none of md5, sha1: {hashes!r}")
+        raise CryptError(f"wrapped remote supports none of md5, sha1, quickxor: {hashes!r}")
 
     # -------------------------------------------------------------- Fs.put (crypt.go:497)
     def put(self, remote: str, reader, size: int = -1):
         enc = self.cipher.encrypt_data(reader)
         ht = None if self.ignore_checksum else self.hash_type()
-        hasher = None if self.ignore_checksum or self.encrypter_md5 else hashlib.new(ht)
+        # QuickXorHash has no hashlib hasher to tee into: the encrypter takes that hash itself
+        by_enc = self.encrypter_md5 or ht == "quickxor"
+        hasher = None if self.ignore_checksum or by_enc else hashlib.new(ht)
         src = enc if hasher is None else _TeeReader(enc, hasher)
-        if not self.ignore_checksum and self.encrypter_md5:
+        if not self.ignore_checksum and by_enc:
             if ht == "md5":
                 enc.set_md5(True)
             else:

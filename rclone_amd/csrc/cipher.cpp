@@ -503,7 +503,7 @@ struct rc_encrypter {
   int32_t err = RC_NIL;
   bool finished = false;
   // crypt.put's tee hash (crypt.go:516-533) taken by the encrypter itself (rc_encrypter_set_hash;
-  // MD5 or SHA-1, the wrapped remote's Hashes().GetOne()):
+  // MD5, SHA-1 or QuickXorHash, the wrapped remote's Hashes().GetOne()):
   // a worker hashes batch k while the consumer reads it and the next refill seals batch k+1 into
   // the other wire buffer.  md5 covers every byte produced once `job` is done; md5_cur is the
   // state before the batch being served (for a consumer that stops inside a batch).
@@ -683,10 +683,17 @@ extern "C" int64_t rc_encrypter_read(rc_encrypter* fh, uint8_t* p, int64_t n, in
 
 extern "C" void rc_encrypter_nonce(const rc_encrypter* fh, uint8_t out[24]) { memcpy(out, fh->nonce, 24); }
 
-// false (with the message xs_last_error returns) for anything but XS_HASH_MD5 / XS_HASH_SHA1
+// false (with the message xs_last_error returns) for anything but XS_HASH_MD5 / XS_HASH_SHA1 /
+// XS_HASH_QUICKXOR
+// xs_hash_size, restated: the CPU stand-ins of the engine ABI (tests/native) do not implement it
+static size_t hash_size(int32_t type) {
+  return type == XS_HASH_MD5 ? 16 : type == XS_HASH_SHA1 || type == XS_HASH_QUICKXOR ? 20 : 0;
+}
+
 static bool hash_type_ok(int32_t type, const char* who) {
-  if (type == XS_HASH_MD5 || type == XS_HASH_SHA1) return true;
-  xs::set_error("%s: unknown hash type %d (XS_HASH_MD5 = 1, XS_HASH_SHA1 = 2)", who, (int)type);
+  if (hash_size(type)) return true;
+  xs::set_error("%s: unknown hash type %d (XS_HASH_MD5 = 1, XS_HASH_SHA1 = 2, XS_HASH_QUICKXOR = 0x40000000)", who,
+                (int)type);
   return false;
 }
 
@@ -708,7 +715,7 @@ extern "C" int32_t rc_encrypter_set_md5(rc_encrypter* fh, int32_t on) {
 }
 
 extern "C" int32_t rc_encrypter_md5(rc_encrypter* fh, uint8_t out[16]) {
-  return rc_encrypter_hash(fh, out, 16);  // RC_ERR_INVALID when the tee is SHA-1's (20 bytes)
+  return rc_encrypter_hash(fh, out, 16);  // RC_ERR_INVALID when the tee's digest has 20 bytes
 }
 
 extern "C" int32_t rc_encrypter_hash(rc_encrypter* fh, uint8_t* out, uint64_t cap) {
@@ -1105,7 +1112,7 @@ extern "C" int32_t rc_hash_batch_with_nonce(rc_cipher* c, uint64_t n, const rc_r
 extern "C" int32_t rc_hash_batch_with_nonce_type(rc_cipher* c, int32_t type, uint64_t n, const rc_reader* srcs,
                                                  const uint8_t* nonces, uint8_t* md5, int32_t* errs) {
   if (!hash_type_ok(type, "rc_hash_batch_with_nonce_type")) return RC_ERR_INVALID;
-  const size_t hs = type == XS_HASH_SHA1 ? 20 : 16;  // digest stride
+  const size_t hs = hash_size(type);  // digest stride
   if (n == 0) return RC_NIL;
   if (!c || !srcs || !nonces || !md5 || !errs) return RC_ERR_INVALID;
   PinnedBuf buf;

@@ -15,6 +15,7 @@
 //      so many more streams than cores (a high --checkers) still progress together.
 // A SHA-1 stream (a wrapped remote whose hash is SHA-1; xs_host_sha1.h) takes tiers 1 and 2 only:
 // the 16-stream engine is MD5's, so past the CPU budget a SHA-1 job is hashed on its caller's thread.
+// A QuickXorHash stream (OneDrive; xs_host_quickxor.h) does the same.
 // A stream submits its jobs one at a time (it waits for job k before submitting job k+1), so its
 // bytes are hashed in order whichever tier takes each job.
 #pragma once
@@ -38,17 +39,21 @@
 #include "md5_x16.h"
 #include "rc_internal.h"
 #include "xs_host_md5.h"
+#include "xs_host_quickxor.h"
 #include "xs_host_sha1.h"
 
 namespace xs {
 
 class Md5Workers;
 struct Md5Job {
-  // the stream's state, tagged by which pointer is set: st (MD5), or sha (SHA-1) with st == nullptr
+  // the stream's state, tagged by which pointer is set: st (MD5), or sha (SHA-1) or qx
+  // (QuickXorHash) with st == nullptr
   HostMd5* st = nullptr;
   HostSha1* sha = nullptr;
+  HostQuickXor* qx = nullptr;
   void hash() {  // tiers 1 and 2: the job's bytes into its state, on this thread
-    if (sha) sha->update(p, n);
+    if (qx) qx->update(p, n);
+    else if (sha) sha->update(p, n);
     else st->update(p, n);
   }
   const uint8_t* p = nullptr;
@@ -60,25 +65,29 @@ struct Md5Job {
   size_t nblk = 0;
 };
 
-// One stream's hash state for either type (copyable, like the hashers): what the encrypter's tee
+// One stream's hash state for any type (copyable, like the hashers): what the encrypter's tee
 // and computeHashWithNonce keep per stream and point their jobs at.
 struct HashState {
   int type = XS_HASH_MD5;
   HostMd5 md5;
   HostSha1 sha1;
+  HostQuickXor qx;
   explicit HashState(int t = XS_HASH_MD5) : type(t) {}
-  size_t size() const { return type == XS_HASH_SHA1 ? 20 : 16; }
+  size_t size() const { return type == XS_HASH_MD5 ? 16 : 20; }
   void update(const uint8_t* p, size_t n) {
-    if (type == XS_HASH_SHA1) sha1.update(p, n);
+    if (type == XS_HASH_QUICKXOR) qx.update(p, n);
+    else if (type == XS_HASH_SHA1) sha1.update(p, n);
     else md5.update(p, n);
   }
   void final(uint8_t* out) {
-    if (type == XS_HASH_SHA1) sha1.final(out);
+    if (type == XS_HASH_QUICKXOR) qx.final(out);
+    else if (type == XS_HASH_SHA1) sha1.final(out);
     else md5.final(out);
   }
   void bind(Md5Job* j) {  // j hashes into this state
-    j->st = type == XS_HASH_SHA1 ? nullptr : &md5;
+    j->st = type == XS_HASH_MD5 ? &md5 : nullptr;
     j->sha = type == XS_HASH_SHA1 ? &sha1 : nullptr;
+    j->qx = type == XS_HASH_QUICKXOR ? &qx : nullptr;
   }
 };
 
@@ -123,7 +132,7 @@ class Md5Workers {
     }
     // scalar chains already on host cores: busy workers + callers hashing now
     const int on_cores = inline_.load(std::memory_order_relaxed) + busy_workers_.load(std::memory_order_relaxed);
-    if (!lanes_on_ || on_cores < budget_ || j->sha) {  // the x16 lane tier is taken only by MD5 jobs
+    if (!lanes_on_ || on_cores < budget_ || !j->st) {  // the x16 lane tier is taken only by MD5 jobs
       inline_.fetch_add(1, std::memory_order_relaxed);
       j->hash();
       inline_.fetch_sub(1, std::memory_order_relaxed);

@@ -23,8 +23,10 @@
 #include <vector>
 
 #include "xs_host_md5.h"
+#include "xs_host_quickxor.h"
 #include "xs_host_sha1.h"
 #include "xs_internal.h"
+#include "xs_quickxor.h"
 #include "xs_sha1.h"
 #include "xs_topo.h"
 
@@ -300,18 +302,26 @@ int xs_md5_batch_dev(const xs_md5_desc* d_desc, uint64_t n, const void* d_src, u
   return XS_OK;
 }
 
-// ---- hash types (rclone's hash.Type values, fs/hash/hash.go:43)
-size_t xs_hash_size(int type) { return type == XS_HASH_MD5 ? 16 : type == XS_HASH_SHA1 ? 20 : 0; }
+// ---- hash types (rclone's hash.Type values, fs/hash/hash.go:43; XS_HASH_QUICKXOR is our own)
+size_t xs_hash_size(int type) {
+  return type == XS_HASH_MD5 ? 16 : type == XS_HASH_SHA1 || type == XS_HASH_QUICKXOR ? 20 : 0;
+}
 
-// false (with the error set) for anything but XS_HASH_MD5 / XS_HASH_SHA1
+uint64_t xs_quickxor_slice(void) { return kQuickXorSlice; }
+
+// false (with the error set) for anything but XS_HASH_MD5 / XS_HASH_SHA1 / XS_HASH_QUICKXOR
 static bool hash_type_ok(int type, const char* who) {
   if (xs_hash_size(type)) return true;
-  set_error("%s: unknown hash type %d (XS_HASH_MD5 = 1, XS_HASH_SHA1 = 2)", who, type);
+  set_error("%s: unknown hash type %d (XS_HASH_MD5 = 1, XS_HASH_SHA1 = 2, XS_HASH_QUICKXOR = 0x40000000)", who,
+            type);
   return false;
 }
 
+// max_len: an upper bound of the longest stream (QuickXorHash's slice count; the lane-per-object
+// kernels take no hint)
 static hipError_t launch_hash(int type, const xs_hash_desc* d, uint64_t n, const uint8_t* src, uint64_t src_len,
-                              uint8_t* digest, uint8_t* ok, hipStream_t stream) {
+                              uint8_t* digest, uint8_t* ok, uint64_t max_len, hipStream_t stream) {
+  if (type == XS_HASH_QUICKXOR) return launch_quickxor(d, n, src, src_len, digest, ok, max_len, stream);
   return type == XS_HASH_SHA1 ? launch_sha1(d, n, src, src_len, digest, ok, stream)
                               : launch_md5(d, n, src, src_len, digest, ok, stream);
 }
@@ -324,7 +334,8 @@ int xs_hash_batch_dev(int type, const xs_hash_desc* d_desc, uint64_t n, const vo
     set_error("xs_hash_batch_dev: null argument or digest buffer not 4-byte aligned");
     return XS_ERR_INVALID;
   }
-  hipError_t e = launch_hash(type, d_desc, n, (const uint8_t*)d_src, src_len, d_digest, d_ok, (hipStream_t)stream);
+  hipError_t e =
+      launch_hash(type, d_desc, n, (const uint8_t*)d_src, src_len, d_digest, d_ok, src_len, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "hash launch");
   return XS_OK;
 }
@@ -332,7 +343,12 @@ int xs_hash_batch_dev(int type, const xs_hash_desc* d_desc, uint64_t n, const vo
 // prefix || body on this thread, the host tier's hashers
 static void host_hash(int type, const uint8_t* prefix, size_t prefix_len, const uint8_t* body, uint64_t len,
                       uint8_t* out) {
-  if (type == XS_HASH_SHA1) {
+  if (type == XS_HASH_QUICKXOR) {
+    HostQuickXor m;
+    m.update(prefix, prefix_len);
+    m.update(body, len);
+    m.final(out);
+  } else if (type == XS_HASH_SHA1) {
     HostSha1 m;
     m.update(prefix, prefix_len);
     m.update(body, len);
@@ -1339,11 +1355,18 @@ static int host_md5_threads_default() {
 // lane the same 0.24 s is ~11 MiB, too close to 16 to justify a second threshold.
 constexpr uint64_t kHostMd5Min = 16ull << 20;
 
+// QuickXorHash in the engine: objects longer than this are launched apart from the shorter ones of
+// their group (seal_md5_impl), each part with a grid sized by its own longest object
+constexpr uint64_t kQuickXorLong = 1ull << 20;
+
 // Which objects of a group go to the host (route[k] = 1): take the longest first while the host
 // pool's makespan stays below that object's GPU lane time, i.e. while moving it shortens the
 // group (the group's GPU MD5 time is then set by the longest object left on the GPU).
 static void route_host_md5(int type, const uint64_t* wire_len, size_t n, int threads, std::vector<uint8_t>& route) {
   route.assign(n, 0);
+  // QuickXorHash is no dependency chain: the kernel splits one object over the whole device, so
+  // nothing is routed to the host and the host pool is never started
+  if (type == XS_HASH_QUICKXOR) return;
   if (threads <= 0 || n == 0) return;
   std::vector<size_t> order;
   for (size_t k = 0; k < n; k++)
@@ -1513,6 +1536,31 @@ static int seal_md5_impl(xs_engine* e, int type, const uint8_t key[32], uint64_t
       w += (wlen[i - o0] + 15) & ~15ull;
     }
     const uint64_t ngpu = mdesc.size();
+    // QuickXorHash: the launcher sizes its grid by the longest object, so a skewed group (one
+    // multi-GiB object among thousands of small ones) is launched in two parts, the short objects
+    // first in the descriptor array and the long ones after them
+    uint64_t nshort = ngpu, longest = 0, longest_short = 0;
+    if (type == XS_HASH_QUICKXOR) {
+      std::vector<size_t> perm(ngpu);
+      for (size_t k = 0; k < ngpu; k++) perm[k] = k;
+      const auto mid = std::stable_partition(perm.begin(), perm.end(),
+                                             [&](size_t k) { return mdesc[k].len <= kQuickXorLong; });
+      nshort = (uint64_t)(mid - perm.begin());
+      if (nshort > 0 && nshort < ngpu) {
+        std::vector<xs_md5_desc> md(ngpu);
+        std::vector<uint64_t> go(ngpu);
+        for (size_t k = 0; k < ngpu; k++) {
+          md[k] = mdesc[perm[k]];
+          go[k] = gpu_obj[perm[k]];
+        }
+        mdesc.swap(md);
+        gpu_obj.swap(go);
+      }
+      for (size_t k = 0; k < ngpu; k++) {
+        longest = std::max(longest, mdesc[k].len);
+        if (k < nshort) longest_short = std::max(longest_short, mdesc[k].len);
+      }
+    }
     if (!grow(&hb.d_plain, &hb.plain_cap, span) || !grow(&hb.d_body, &hb.body_cap, bsum) ||
         !grow(&hb.d_desc, &hb.desc_cap, nblk * sizeof(xs_block_desc)) ||
         !grow(&hb.d_mdesc, &hb.mdesc_cap, std::max<uint64_t>(ngpu, 1) * sizeof(xs_md5_desc)) ||
@@ -1564,7 +1612,15 @@ static int seal_md5_impl(xs_engine* e, int type, const uint8_t key[32], uint64_t
     }
     if (err != hipSuccess) return hip_fail(err, "D2H");
     if (ngpu) {
-      err = launch_hash(type, (const xs_md5_desc*)hb.d_mdesc, ngpu, hb.d_body, bsum, hb.d_digest, nullptr, st);
+      const xs_md5_desc* dm = (const xs_md5_desc*)hb.d_mdesc;
+      if (type == XS_HASH_QUICKXOR && nshort > 0 && nshort < ngpu) {
+        err = launch_hash(type, dm, nshort, hb.d_body, bsum, hb.d_digest, nullptr, longest_short, st);
+        if (err == hipSuccess)
+          err = launch_hash(type, dm + nshort, ngpu - nshort, hb.d_body, bsum, hb.d_digest + hs * nshort, nullptr,
+                            longest, st);
+      } else {
+        err = launch_hash(type, dm, ngpu, hb.d_body, bsum, hb.d_digest, nullptr, longest, st);
+      }
       if (err != hipSuccess) return hip_fail(err, "md5");
       dig.resize(hs * ngpu);
       err = hipMemcpyAsync(dig.data(), hb.d_digest, ngpu * hs, hipMemcpyDeviceToHost, st);

@@ -194,17 +194,18 @@ def md5_batch(desc, src: torch.Tensor):
 
 
 HASH_MD5, HASH_SHA1 = 1, 2  # XS_HASH_* (rclone's hash.Type values)
+HASH_QUICKXOR = 0x40000000  # XS_HASH_QUICKXOR (OneDrive's QuickXorHash; the library's own value)
 HASH_DESC_BYTES = MD5_DESC_BYTES
 
 
 def hash_batch(hash_type, desc, src: torch.Tensor):
-    """MD5 or SHA-1 of many streams in HBM (xs_hash_batch_dev): hash_type "md5" / "sha1" (or
-    HASH_MD5 / HASH_SHA1), desc as for md5_batch; returns (digests uint8 [n, 16 or 20], ok uint8
-    [n]) on the device."""
-    ht = {"md5": HASH_MD5, "sha1": HASH_SHA1}.get(hash_type, hash_type)
+    """MD5, SHA-1 or QuickXorHash of many streams in HBM (xs_hash_batch_dev): hash_type "md5" /
+    "sha1" / "quickxor" (or HASH_MD5 / HASH_SHA1 / HASH_QUICKXOR), desc as for md5_batch; returns
+    (digests uint8 [n, 16 or 20], ok uint8 [n]) on the device."""
+    ht = {"md5": HASH_MD5, "sha1": HASH_SHA1, "quickxor": HASH_QUICKXOR}.get(hash_type, hash_type)
     hs = _lib.lib().xs_hash_size(ht) if isinstance(ht, int) else 0
     if hs == 0:
-        raise ValueError(f"unsupported hash type {hash_type!r} (md5, sha1)")
+        raise ValueError(f"unsupported hash type {hash_type!r} (md5, sha1, quickxor)")
     _require_gpu(src)
     if isinstance(desc, torch.Tensor):
         _require_gpu(desc)
